@@ -8,17 +8,35 @@ the step kernel (early terminations too). One "step" = one BoatEnv.step over
 all envs of the rank (+ at N>1 pooling the step's full transitions -- record,
 action and terminal obs -- for a shared replay buffer over RCCL).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
-Timing. Steps run in whole 256-step segments: each segment is one hipGraph of
-256 step launches followed by the slot refill (k_need_masks + k_refill +
-k_refill_fit: the RNG draws and spline fits of the episodes that replace the
-ended ones), which the engine needs at least every 256 steps. W and K are
-rounded UP to whole segments (at least one each), so the timed region always
-starts on a segment boundary and always holds its share of refills; the JSON
-``steps`` / ``warmup`` are the step counts actually executed (the requested
-ones are in ``requested``). The timed region is bracketed by barrier +
-synchronize; value = all envs x steps / max-over-ranks time.
+A plain run does what the headline figure needs and nothing else: set up, warm
+up, time the K steps, write the outputs (``--dump-outputs``), print the line.
+``--full`` adds every side measurement (the CPU baseline, the every-output
+rollout, the replay paths at one GPU, the other exchanges at N>1, the
+kernel-only launches after an N>1 or eager timed region) and sizes the timed
+region as the earlier rounds did (below).
+
+Timing. Steps run in 256-step segments: each segment is one persistent launch
+(or one hipGraph of 256 step launches) followed by the slot refill
+(k_need_masks + k_refill + k_refill_fit: the RNG draws and spline fits of the
+episodes that replace the ended ones), which the engine needs at least every
+256 steps. A plain one-GPU run times exactly K steps: K // 256 whole segments
+and, if K is no multiple of 256, one shorter launch of the remaining steps,
+each followed by its refill (N>1: whole segments, the exchange's unit). With
+``--full`` K is rounded UP to whole segments, at least 8 of them and at least
+``--min-seconds`` of them. W is rounded up to whole segments in both (a GPU
+run warms up at least 24: past the clock boost), so the timed region always
+starts on a segment boundary; the JSON ``steps`` / ``warmup`` are the step
+counts actually executed (the requested ones are in ``requested``). The timed
+region is bracketed by barrier + synchronize; value = all envs x steps /
+max-over-ranks time.
+
+``--dump-outputs DIR``: after the timed steps, what the last timed step left
+in the env's output buffers (what ``VecBoatEnv.step`` returns: obs, reward,
+done, term, the terminal obs of the envs that ended) and the carried f64
+state, one ``DIR/<name>.npy`` each. Seeds, actions and (in a plain run) step
+counts are fixed, so two builds can be compared array for array.
 
 Roofline: algorithmic bytes per env-step x envs, over the kernel's average
 per-step duration from HIP events on the kernel's stream (refills excluded;
@@ -29,7 +47,7 @@ default): the same components with the state resident in registers for the
 rate is reported beside it). ``traffic`` = HBM bytes per step from the
 committed rocprofv3 PMC passes (tools/pmc.sh).
 
-cpu_baseline: SURVEY.md §8(d) C1 -- the reference step restated
+cpu_baseline (``--full``): SURVEY.md §8(d) C1 -- the reference step restated
 (oracle/boat_oracle.py) at ONE env per process, as the reference runs, on one
 core and on all cores of the lease (tools/cpu_c1.py, a child process), for
 the bench's experiment; the vectorised numpy port on the bench's env count is
@@ -79,17 +97,24 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=2048)
     ap.add_argument("--warmup", type=int, default=512)
     ap.add_argument("--envs", type=int, default=65536, help="envs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (CPU baseline, every-output rollout, replay paths, "
+                         "the other exchanges at N>1, kernel-only launches) and size the timed region in whole "
+                         "segments for at least --min-seconds; a plain run times exactly --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left in the env's output "
+                         "buffers (and the carried f64 state) as DIR/<name>.npy")
     ap.add_argument("--min-seconds", type=float, default=MIN_TIMED_SECONDS,
-                    help="the timed region lasts at least this long (whole segments; GPU runs only)")
+                    help="--full: the timed region lasts at least this long (whole segments; GPU runs only)")
     ap.add_argument("--experiment", type=int, default=6)
     ap.add_argument("--no-graph", action="store_true", help="eager per-step launches (--launch step)")
     ap.add_argument("--launch", choices=("segment", "step"), default="segment",
                     help="segment: one persistent sacenv_boat_segment launch per 256 steps (state in "
                          "registers, actions behind per-wave flags); step: one k_step launch per step, "
                          "256 of them per hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="total CPU-baseline budget (4 C1 legs + the vectorised port)")
+                    help="--full: total CPU-baseline budget (4 C1 legs + the vectorised port)")
     ap.add_argument("--kernel-launches", type=int, default=256)
     ap.add_argument("--test-mode", type=int, default=0, help="1 = rudder frozen (no terminations)")
     ap.add_argument("--helpers", type=int, default=None,
@@ -138,7 +163,7 @@ def parse(argv=None):
                          "for roofline.kernel_avg_us: each pair puts a stream marker on both sides of "
                          "the launch (measured: every segment 1.78 us/step, every 4th 1.74)")
     ap.add_argument("--no-every-output", action="store_true",
-                    help="skip the every-output rollout measurement after the timed region (PMC passes: its "
+                    help="--full: skip the every-output rollout measurement after the timed region (PMC passes: its "
                          "k_rollout launches would mix into the segment kernel's counters)")
     ap.add_argument("--closed-loop", action="store_true",
                     help="a separate line: the SAC actor choosing every step's actions on the device, handing "
@@ -597,10 +622,23 @@ class SegmentRunner:
     def _clock_pair(self):
         return self._clocks.pop() if self._clocks else (_Clock(self.dev), _Clock(self.dev))
 
-    def _steps(self, k0: int, with_pool: bool, buf=None, on_step=None, timed: bool = False) -> None:
-        """The SEG steps of one segment, enqueued (captured, eager or persistent)."""
+    def _steps(self, k0: int, with_pool: bool, buf=None, on_step=None, timed: bool = False,
+               n: int = SEG) -> None:
+        """The SEG steps of one segment (or its first n: no pooling then), enqueued
+        (captured, eager or persistent)."""
         wl, p = self.wl, self.pool if with_pool else None
         x = self.exchange if with_pool else None
+        if n != SEG:        # a short segment: the steps alone (rows and exchanges take whole segments)
+            if p is not None or x is not None or not 0 < n < SEG:
+                raise ValueError("a short segment has 1 .. SEG-1 steps and no pooling")
+            if self.mode == "segment":
+                wl.segment_step(k0, n)
+                return
+            for k in range(k0, k0 + n):
+                wl.stepper(wl.actions[k % ACTION_STEPS])
+                if on_step is not None:
+                    on_step(k)
+            return
         if x is not None:   # the segment writes the staged replay's rows
             sa = x.stage_args()
             if self.mode == "segment":
@@ -710,9 +748,13 @@ class SegmentRunner:
         if self.exchange is not None:
             self.exchange.wait()
 
-    def segment(self, k0: int, timed: bool = False, with_pool: bool = True, on_step=None) -> int:
+    def segment(self, k0: int, timed: bool = False, with_pool: bool = True, on_step=None, n: int = SEG) -> int:
         """Steps k0 .. k0+SEG-1 (k0 % SEG == 0), then the refill, then the pooling
-        (all-gather) or the replay exchange."""
+        (all-gather) or the replay exchange. n < SEG: a short segment, steps k0 .. k0+n-1
+        in one launch (eager launches in the graph and eager modes) and the refill; a runner
+        with a pool or an exchange takes whole segments only."""
+        if n != SEG and (self.pool is not None or self.exchange is not None):
+            raise ValueError("a runner that pools or exchanges rows steps whole segments")
         x = self.exchange if with_pool else None
         if x is not None:
             if not x.started:  # the replay buffer starts here: s of its first row = the current obs
@@ -732,14 +774,14 @@ class SegmentRunner:
         if own:
             ea, eb = self._clock_pair()
             ea.record(self.st)
-        if self.graphs is not None:
+        if self.graphs is not None and n == SEG:
             gset = self.graphs[(k0 % ACTION_STEPS) // SEG]
             gset[p.buf if p is not None else 0].replay()
         else:
-            self._steps(k0, with_pool, buf=buf, on_step=on_step, timed=timed)
+            self._steps(k0, with_pool, buf=buf, on_step=on_step, timed=timed, n=n)
         if own:
             eb.record(self.st)
-            self.seg_events.append((ea, eb, SEG))
+            self.seg_events.append((ea, eb, n))
         if x is not None:
             x.launched()
         self.wl.refill()
@@ -748,7 +790,7 @@ class SegmentRunner:
             p.flush()
         if x is not None:
             x.after()
-        return k0 + SEG
+        return k0 + n
 
 
 # ---------------------------------------------------------------- timing loop
@@ -873,7 +915,15 @@ def run_bench(args, rank: int, world: int, dev, wl: Workload):
     st = run.st
     seg_events = run.seg_events
     segment = run.segment
-    n_warm, n_timed = warm_segs(args.warmup), timed_segs(args.steps)
+    full = bool(getattr(args, "full", False))
+    rows = pool is not None or exchange is not None
+    n_warm = warm_segs(args.warmup)
+    if full:
+        n_timed, n_tail = timed_segs(args.steps), 0
+    elif rows:   # the rows of a segment are pooled / exchanged whole
+        n_timed, n_tail = segs(args.steps), 0
+    else:        # exactly --steps steps: whole segments and one shorter launch
+        n_timed, n_tail = divmod(max(1, int(args.steps)), SEG)
     if dev.type == "cuda":  # past the clock boost (~20 launches) before the rate is sized
         n_warm = max(n_warm, WARM_BOOST_SEGS)
     k = 0
@@ -888,19 +938,21 @@ def run_bench(args, rank: int, world: int, dev, wl: Workload):
     run.finish()
     _sync(dev)
     per_seg = (time.perf_counter() - t_w) / (n_warm - half)
-    if dev.type == "cuda":  # (CPU stub runs measure the harness: no minimum duration)
+    if full and dev.type == "cuda":  # (CPU stub runs measure the harness: no minimum duration)
         want = math.ceil(args.min_seconds * TIMED_MARGIN / max(per_seg, 1e-6))
         n_timed = int(_max_over_ranks(float(max(n_timed, want)), world, dev))
     barrier(world)
     _sync(dev)
     ev0, ev1 = _Clock(dev), _Clock(dev)
-    run.reserve_clocks(2 * n_timed)
+    run.reserve_clocks(2 * (n_timed + 1))
     t0 = time.perf_counter()
     ev0.record(st)
     g0 = pool.flushes if pool is not None else 0
     x0 = exchange.exchanges if exchange is not None else 0
     for _ in range(n_timed):
         k = segment(k, True)
+    if n_tail:
+        k = segment(k, True, n=n_tail)
     run.finish()  # the last segment's all-gather / exchange and the last refills are inside the timed region
     ev1.record(st)
     gathers_timed = (pool.flushes if pool is not None else 0) - g0
@@ -908,10 +960,13 @@ def run_bench(args, rank: int, world: int, dev, wl: Workload):
     _sync(dev)
     barrier(world)
     el = time.perf_counter() - t0
-    steps = n_timed * SEG
+    steps = n_timed * SEG + n_tail
     el_max = _max_over_ranks(el, world, dev)
     if exchange is not None:  # (after the timed region: it synchronises)
         exchange.check()
+    dumped = None
+    if getattr(args, "dump_outputs", None):  # before anything else steps the envs
+        dumped = dump_outputs(args.dump_outputs, wl, rank, world)
 
     # the kernel's average launch duration from events on the stream it runs on,
     # refills excluded. N=1: the launches of the timed region itself. N>1 (the
@@ -920,7 +975,12 @@ def run_bench(args, rank: int, world: int, dev, wl: Workload):
     what = ("persistent sacenv_boat_segment launches" if run.mode == "segment" else
             f"graph-replayed {SEG}-launch k_step segments")
     no_exchange = all_gather = None
-    if pool is not None or exchange is not None or run.mode == "eager":
+    kern_src = None
+    if not full and (rows or run.mode == "eager"):
+        # a plain run times no launches of its own for the kernel: the timed region's wrote the
+        # exchanged rows (N>1) or were eager launches, so the line carries no roofline
+        seg_events.clear()
+    elif rows or run.mode == "eager":
         if run.mode == "eager" and dev.type == "cuda" and not args.no_graph:
             run.capture_all(with_pool=False)
             run.mode, use_graph = "graph", True
@@ -964,14 +1024,15 @@ def run_bench(args, rank: int, world: int, dev, wl: Workload):
     else:
         kern_src = (f"HIP events around the {len(seg_events)} {what} of the timed region (refills "
                     "between segments excluded)")
-    kern_s = sum(a.ms_to(b) for a, b, _ in seg_events) * 1e-3 / sum(n for _, _, n in seg_events)
+    kern_s = (sum(a.ms_to(b) for a, b, _ in seg_events) * 1e-3 / sum(n for _, _, n in seg_events)
+              if seg_events else None)
     step_s = ev0.ms_to(ev1) * 1e-3 / steps
 
     every = replay_path = standin_path = rank_path = None
-    if (world == 1 and run.mode == "segment" and not args.mixed and not args.no_autoreset
+    if (full and world == 1 and run.mode == "segment" and not args.mixed and not args.no_autoreset
             and not args.no_every_output):
         every = every_output_rate(wl, dev, k0=k)
-    if world == 1 and not args.mixed and not args.no_autoreset and not args.no_every_output and (
+    if full and world == 1 and not args.mixed and not args.no_autoreset and not args.no_every_output and (
             run.mode == "segment" or args.stub):
         # the sharded pooling's replay path on one GPU (no collective): rows staged, the
         # segment's learns sampled on a side stream overlapped with the next segment
@@ -1024,9 +1085,12 @@ def run_bench(args, rank: int, world: int, dev, wl: Workload):
     algo_step = SEG_MIN_BYTES * N if seg_mode else wl.bytes_per_launch
     if seg_mode and args.mixed:  # + the toys with their state resident: record 14 B per step
         algo_step += sum(TOY_SEG_BYTES.values()) * N
-    achieved = algo_step / kern_s
-    traffic = None if args.mixed or args.stub else load_traffic(N, args.experiment, "segment" if seg_mode else "step")
-    compute = load_compute(N, args.experiment, kern_s) if seg_mode and not args.mixed and not args.stub else None
+    have_kern = kern_s is not None   # (a plain N>1 or eager run has no kernel time: roofline null)
+    achieved = algo_step / kern_s if have_kern else None
+    traffic = (None if args.mixed or args.stub or not have_kern else
+               load_traffic(N, args.experiment, "segment" if seg_mode else "step"))
+    compute = (load_compute(N, args.experiment, kern_s)
+               if have_kern and seg_mode and not args.mixed and not args.stub else None)
     if compute is not None and world > 1:
         compute["note"] += f" (PMC from the one-GPU run in {compute['source']}, applied to this run's kernel time)"
     backend = None
@@ -1088,9 +1152,18 @@ def run_bench(args, rank: int, world: int, dev, wl: Workload):
         "steps": steps,
         "warmup": n_warm * SEG,
         "requested": {"steps": args.steps, "warmup": args.warmup,
-                      "rule": f"rounded up to whole {SEG}-step segments (each ends with its refill); "
-                              f"at least {MIN_TIMED_SEGS * SEG} timed and {MIN_WARMUP_SEGS * SEG} warm-up steps, "
-                              f"and timed segments for at least ~{args.min_seconds:g} s at the warm-up's rate"},
+                      "rule": (f"rounded up to whole {SEG}-step segments (each ends with its refill); "
+                               f"at least {MIN_TIMED_SEGS * SEG} timed and {MIN_WARMUP_SEGS * SEG} warm-up steps, "
+                               f"and timed segments for at least ~{args.min_seconds:g} s at the warm-up's rate"
+                               if full else
+                               (f"the timed steps rounded up to whole {SEG}-step segments (the exchange's unit)"
+                                if rows else
+                                f"the timed steps as asked: whole {SEG}-step segments and one shorter launch of "
+                                "the rest") +
+                               f", each ending with its refill; the warm-up rounded up to whole segments, at least "
+                               f"{MIN_WARMUP_SEGS * SEG} steps ({WARM_BOOST_SEGS * SEG} on a GPU: past the clock "
+                               "boost)")},
+        "full": full,
         "setup": {"graph_first_replays": run.first_replays,
                   "note": "steps of the first pass over the action table (a captured graph's first "
                           "replay carries its device upload), run before the warm-up, untimed"},
@@ -1128,7 +1201,8 @@ def run_bench(args, rank: int, world: int, dev, wl: Workload):
                    "refill": None if args.no_autoreset else (
                        f"k_need_masks + k_refill + k_refill_fit after every {SEG}-step segment, inside the "
                        "timed region")},
-        "roofline": {"bound": "fp64-issue" if compute is not None else "hbm",
+        "roofline": None if not have_kern else {
+                     "bound": "fp64-issue" if compute is not None else "hbm",
                      "achieved": compute["achieved"] if compute is not None else achieved / 1e9,
                      "peak": compute["peak"] if compute is not None else HBM_PEAK / 1e9,
                      "unit": "TFLOP/s" if compute is not None else "GB/s",
@@ -1180,7 +1254,63 @@ def run_bench(args, rank: int, world: int, dev, wl: Workload):
         "cpu_baseline": None,
         "dist": dinfo,
         "pooling": pooling_out,
+        "outputs": dumped,
     }
+
+
+# ---------------------------------------------------------------- outputs
+DUMP_MAX_ENVS = 131072   # <= ~260 B per env over all arrays: the files stay well under 64 MB
+
+
+def dump_outputs(path: str, wl: Workload, rank: int = 0, world: int = 1) -> dict:
+    """Write what the last step left for its caller as ``path/<name>.npy`` (f32 / f64):
+    per env type the step's outputs (obs, reward, done, term as ``VecBoatEnv.step``
+    returns them; final_obs and final_ep_reward where the env ended in that step, 0
+    elsewhere: they are only valid there; the cumulative termination counters) and, for
+    the boat, the carried f64 state. Above DUMP_MAX_ENVS envs a fixed seeded sample of
+    them (``<type>_env_index.npy``). N>1: each rank writes ``rank<r>_<name>.npy``."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for env in wl.envs:
+        if hasattr(env, "device") and torch.device(env.device).type == "cuda":
+            torch.cuda.synchronize(env.device)
+    names = ["boat"] + [type(e).__name__.replace("Env", "").lower() for e in wl.envs[1:]]
+    written, total = [], 0
+
+    def save(name, arr):
+        nonlocal total
+        arr = np.ascontiguousarray(arr, dtype=np.float64 if arr.dtype == np.float64 else np.float32)
+        fn = (f"rank{rank}_" if world > 1 else "") + name + ".npy"
+        np.save(os.path.join(path, fn), arr)
+        written.append(fn)
+        total += arr.nbytes
+
+    for name, env in zip(names, wl.envs):
+        n = int(env.num_envs)
+        pick = None
+        if n > DUMP_MAX_ENVS:
+            pick = np.sort(np.random.default_rng(20240229).choice(n, DUMP_MAX_ENVS, replace=False))
+            save(f"{name}_env_index", pick.astype(np.float64))
+
+        def host(t, axis=0):
+            a = t.detach().cpu().numpy()
+            return a if pick is None else np.take(a, pick, axis=axis)
+
+        done = host(env.done).astype(bool) if hasattr(env, "done") else None
+        for fld in ("obs", "reward", "done", "term"):
+            if hasattr(env, fld):
+                save(f"{name}_{fld}", host(getattr(env, fld)))
+        for fld in ("final_obs", "final_ep_reward"):
+            if hasattr(env, fld) and done is not None:
+                a = host(getattr(env, fld)).copy()
+                a[~done] = 0
+                save(f"{name}_{fld}", a)
+        if hasattr(env, "counters"):
+            save(f"{name}_counters", host(env.counters, axis=1))
+        if name == "boat" and hasattr(env, "s_x"):
+            for fld in ("s_x", "s_y", "s_r", "v_x", "v_y", "v_r", "rudder", "ep_reward", "t", "index"):
+                save(f"{name}_state_{fld}", host(getattr(env, fld)).astype(np.float64))
+    return {"dir": path, "files": written, "bytes": total}
 
 
 # ---------------------------------------------------------------- every-output rate
@@ -1485,8 +1615,10 @@ def main(argv=None):
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the N rank processes here (before anything touches a GPU)
         sys.exit(spawn_ranks(args.gpus, argv))
+    if args.dump_outputs and (args.rollout or args.closed_loop or args.train):
+        raise SystemExit("--dump-outputs writes the default line's outputs (not --rollout / --closed-loop / --train)")
     cpu = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and not args.rollout
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and not args.rollout
             and not args.closed_loop and not args.train and not args.stub):
         # before anything touches the GPU: the C1 legs are child processes, and an
         # idle host keeps them from competing with the timed region's launches

@@ -20,7 +20,7 @@ import torch.multiprocessing as mp
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from bench_stub import N_PAD, workload as _stub_workload  # noqa: E402
+from bench_stub import N_ENVS, N_PAD, workload as _stub_workload  # noqa: E402
 
 
 def _workload(bench, rank):
@@ -36,7 +36,7 @@ def _run(rank, world, argv):
 
 
 def test_driver_command_world1_rounds_to_whole_segments():
-    out, env = _run(0, 1, ["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    out, env = _run(0, 1, ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
     assert out["steps"] == 8 * 256 and out["warmup"] == 512   # at least 8 timed, 2 warm-up segments
     assert out["requested"] == {"steps": 20, "warmup": 5, "rule": out["requested"]["rule"]}
     # every segment ends with its refill; timed region = eight whole segments (+ k_step segs after)
@@ -58,10 +58,37 @@ def test_metric_follows_the_config():
 
 @pytest.mark.parametrize("steps,warmup,n_timed", [(20, 5, 8), (300, 0, 8), (2100, 0, 9)])
 def test_segment_rounding(steps, warmup, n_timed):
-    out, env = _run(0, 1, ["--steps", str(steps), "--warmup", str(warmup), "--kernel-launches", "1"])
+    out, env = _run(0, 1, ["--steps", str(steps), "--warmup", str(warmup), "--kernel-launches", "1", "--full"])
     assert out["steps"] == n_timed * 256
     # warmup segs + timed segs + 2 k_step-only segments (eager path), each with a refill
     assert env.refills == out["warmup"] // 256 + n_timed + 2
+
+
+@pytest.mark.parametrize("steps,launches", [(1, 1), (20, 1), (256, 1), (300, 2), (2100, 9)])
+def test_plain_run_times_exactly_the_steps_asked(steps, launches):
+    """Without --full: --steps sets the timed steps (whole segments + one shorter launch, a
+    refill after each), nothing runs after the timed region, and no side measurement is made."""
+    out, env = _run(0, 1, ["--gpus", "1", "--steps", str(steps), "--warmup", "5"])
+    assert out["steps"] == steps and out["warmup"] == 512 and out["full"] is False
+    assert out["requested"]["steps"] == steps
+    assert env.steps == out["warmup"] + steps
+    assert env.refill_at == [256, 512] + [512 + min(256 * (i + 1), steps) for i in range(launches)]
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "env-steps/s"
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - out["config"]["global_envs"]) < 1e-6 * out["value"]
+    for side in ("every_output", "replay_path", "replay_path_collective_standin", "replay_path_rank_of_world",
+                 "cpu_baseline", "roofline", "pooling", "outputs"):
+        assert out[side] is None, side
+    json.dumps(out)
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    import numpy as np
+    d = tmp_path / "dump"
+    out, env = _run(0, 1, ["--steps", "300", "--warmup", "5", "--dump-outputs", str(d)])
+    assert out["outputs"]["files"] == ["boat_obs.npy"] and env.steps == 512 + 300   # nothing stepped after
+    a = np.load(d / "boat_obs.npy")
+    assert a.dtype == np.float32 and a.shape == (N_ENVS, 11)
+    assert out["outputs"]["bytes"] == a.nbytes <= 64 << 20
 
 
 def _free_port():
@@ -87,8 +114,9 @@ def _dist_worker(rank, world, port, q, extra):
         dist.destroy_process_group()
 
 
-def _world2(extra):
+def _world2(extra, full=True):
     world = 2
+    extra = [*extra, "--full"] if full else list(extra)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -139,6 +167,18 @@ def test_driver_command_world2_gloo_sharded_exchange():
     assert ag["value"] > 0 and ag["received_bytes_per_rank"] == 53 * N_PAD * ag["steps"]
     assert po["no_exchange"]["value"] > 0
     assert out["data"].startswith("stub")
+
+
+def test_plain_world2_times_whole_segments_and_nothing_beside():
+    """N>1 without --full: the exchange's unit is the segment, so --steps 20 times one whole
+    segment (one exchange in the timed region); the no-exchange and all-gather runs after the
+    timed region belong to --full."""
+    out = _world2([], full=False)
+    assert out["steps"] == 256 and out["n_gpus"] == 2 and out["value"] > 0 and out["full"] is False
+    po = out["pooling"]
+    assert po["mode"] == "sharded" and po["exchanges_timed"] == 1
+    assert po["no_exchange"] is None and po["all_gather"] is None and out["roofline"] is None
+    assert "1 in the timed region" in out["config"]["collective"]
 
 
 def test_driver_command_world2_gloo_sharded_allreduce():

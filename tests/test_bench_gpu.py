@@ -1,9 +1,11 @@
 """The driver's exact round-end bench command on the GPU (round 1 died on it).
 
-Runs ``python bench.py --gpus 1 --steps 20 --warmup 5`` as a child process
-(with a 1-second CPU-baseline budget) and checks the JSON line: rc 0, whole
-segments executed, ``roofline`` and ``cpu_baseline`` present, and the timed
-steps fit in the wall time of the run.
+Runs ``python bench.py --gpus 1 --steps 20 --warmup 5 --full`` as a child
+process (with a 1-second CPU-baseline budget) and checks the JSON line: rc 0,
+whole segments executed, ``roofline`` and ``cpu_baseline`` present, and the
+timed steps fit in the wall time of the run. The plain command (no ``--full``)
+times exactly the steps asked, measures nothing beside them, and with
+``--dump-outputs`` writes the last step's arrays, the same from run to run.
 """
 import json
 import os
@@ -11,6 +13,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -20,7 +23,7 @@ from conftest import ROOT
 def test_driver_bench_command():
     t0 = time.perf_counter()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20",
-                        "--warmup", "5", "--cpu-seconds", "1"],
+                        "--warmup", "5", "--full", "--cpu-seconds", "1"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     wall = time.perf_counter() - t0
     assert r.returncode == 0, r.stderr[-3000:]
@@ -62,6 +65,71 @@ def test_driver_bench_command():
         assert d["metric"] == json.load(f)["metric"]
 
 
+def _dump_in_process(argv, path, gpu):
+    """bench.py's default line in this process (make_workload + run_bench), dumping to path."""
+    import bench
+    args = bench.parse([*argv, "--dump-outputs", str(path)])
+    out = bench.run_bench(args, 0, 1, gpu, bench.make_workload(args, 0, gpu))
+    return out, {f[:-4]: np.load(os.path.join(path, f)) for f in out["outputs"]["files"]}
+
+
+@pytest.mark.gpu
+def test_plain_bench_command_is_lean_and_dumps_its_outputs(built_lib, gpu, tmp_path):
+    """``bench.py --gpus 1 --steps 300 --warmup 5 --dump-outputs DIR`` (no --full): exactly 300
+    timed steps (one whole segment + a 44-step launch), no side measurement, the headline
+    fields as the full line has them, less than 30 s outside the steps, and the last step's
+    arrays on disk -- bit for bit what a second run (in this process) writes."""
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "300",
+                        "--warmup", "5", "--dump-outputs", str(tmp_path / "a")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 300 and d["warmup"] == 256 * 24 and d["n_gpus"] == 1 and d["full"] is False
+    assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] * 1e-3 / 65536 - 1) < 1e-9
+    with open(os.path.join(ROOT, "BASELINE.json")) as f:
+        assert d["metric"] == json.load(f)["metric"]
+    for side in ("cpu_baseline", "every_output", "replay_path", "replay_path_collective_standin",
+                 "replay_path_rank_of_world", "pooling"):
+        assert d[side] is None, side
+    # the kernel time comes from the timed region's own launches: the roofline stays
+    assert d["roofline"]["bound"] == "fp64-issue" and d["roofline"]["kernel_avg_us"] > 0
+    assert wall - (d["steps"] + d["warmup"]) * d["ms_per_step"] * 1e-3 < 30.0
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(d["outputs"]["files"]) and "boat_obs.npy" in files
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) == d["outputs"]["bytes"] <= 64 << 20
+    assert got["boat_obs"].shape == (65536, 11) and got["boat_state_s_x"].dtype == np.float64
+    # the run is past its transient: envs have ended and restarted, some in the last step
+    assert got["boat_counters"].sum() > 0 and np.isfinite(got["boat_obs"]).all()
+    out, again = _dump_in_process(["--gpus", "1", "--steps", "300", "--warmup", "5"], tmp_path / "b", gpu)
+    assert out["steps"] == 300 and sorted(again) == sorted(got)
+    for name in got:
+        assert np.array_equal(got[name], again[name]), name
+
+
+@pytest.mark.gpu
+def test_plain_bench_short_launch_agrees_across_launch_modes(built_lib, gpu, tmp_path):
+    """--steps 300 = one whole segment + 44 steps: the persistent launch's short segment, the
+    graph mode's eager tail and the eager mode leave the same arrays (4 096 envs)."""
+    base = ["--steps", "300", "--warmup", "5", "--envs", "4096"]
+    outs = [_dump_in_process([*base, *extra], tmp_path / str(i), gpu)
+            for i, extra in enumerate(([], ["--launch", "step"], ["--no-graph"]))]
+    assert [o["steps"] for o, _ in outs] == [300] * 3
+    assert outs[0][0]["roofline"] is not None and outs[2][0]["roofline"] is None   # (eager: --full times it)
+    ref = outs[0][1]
+    assert ref["boat_obs"].shape == (4096, 11) and (ref["boat_state_index"] > 0).any()
+    for _, arrs in outs[1:]:
+        assert sorted(arrs) == sorted(ref)
+        for name in ref:
+            assert np.array_equal(ref[name], arrs[name]), name
+
+
 def _two_rank_env():
     return dict(os.environ, SACENV_BENCH_BACKEND="gloo", SACENV_BENCH_ONE_DEVICE="1")
 
@@ -79,7 +147,7 @@ def test_bench_two_ranks_gloo_on_one_device():
     s.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "20", "--warmup", "5", "--envs", "8192"],
+                        "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--envs", "8192"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=_two_rank_env())
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -97,7 +165,7 @@ def test_bench_self_launch_two_ranks_on_one_device():
     """``python bench.py --gpus 2`` with no launcher: bench starts its own two ranks."""
     env = {k: v for k, v in _two_rank_env().items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-                        "--warmup", "5", "--envs", "4096", "--exchange-segs", "1"],
+                        "--warmup", "5", "--full", "--envs", "4096", "--exchange-segs", "1"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -111,7 +179,7 @@ def test_bench_two_ranks_allreduce_exact_sampler():
     """The previous default, kept as options: the MT-exact draws and the SUM all-reduce."""
     env = {k: v for k, v in _two_rank_env().items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-                        "--warmup", "5", "--envs", "4096", "--exchange-segs", "1", "--sampler", "mt",
+                        "--warmup", "5", "--full", "--envs", "4096", "--exchange-segs", "1", "--sampler", "mt",
                         "--exchange", "allreduce"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -6,7 +6,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-ARGS=${BENCH_ARGS:-"--steps 2000 --warmup 300 --no-cpu-baseline"}
+ARGS=${BENCH_ARGS:-"--full --steps 2000 --warmup 300 --no-cpu-baseline"}
 for round in 1 2; do
   for v in ${VARIANTS:-base}; do
     if [ -d "ab/$v" ]; then

@@ -3,7 +3,7 @@
 # alternating rounds. VARIANTS="base v1 v2"; base = the in-tree library.
 set -o pipefail
 mkdir -p gpurun_out
-ARGS=${BENCH_ARGS:-"--no-cpu-baseline"}
+ARGS=${BENCH_ARGS:-"--full --no-cpu-baseline"}
 for round in $(seq 1 ${ROUNDS:-2}); do
   for v in ${VARIANTS:-base}; do
     if [ "$v" = base ]; then unset SACENV_LIB; else export SACENV_LIB=$PWD/sac-agent_amd/build/libsacenv_$v.so; fi

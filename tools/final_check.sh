@@ -21,7 +21,7 @@ if [ "$P" != 2 ] && [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || exit 1
   tail -1 gpurun_out/smoke.log
 fi
-B="timeout -k 10 300 python bench.py"
+B="timeout -k 10 300 python bench.py --full"   # every line with its side measurements
 if [ "$P" != 2 ]; then
 $B --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_driver.json 2> gpurun_out/bench_driver.log || exit 1
 $B > gpurun_out/bench_default.json 2> gpurun_out/bench_default.log || exit 1
@@ -51,11 +51,11 @@ fi
 [ "$P" = 1 ] && { echo final_check part 1 done; exit 0; }
 # N=2 rehearsals over gloo on the one GPU: the default sharded exchange (bench starting its
 # own ranks, no launcher), and the all-gather under torch.distributed.run
-SACENV_BENCH_BACKEND=gloo SACENV_BENCH_ONE_DEVICE=1 timeout -k 10 400 python bench.py --gpus 2 --envs 65536 \
+SACENV_BENCH_BACKEND=gloo SACENV_BENCH_ONE_DEVICE=1 timeout -k 10 400 python bench.py --full --gpus 2 --envs 65536 \
   --steps 256 --warmup 128 > gpurun_out/rehearse_sharded.json 2> gpurun_out/rehearse_sharded.log \
   || { tail -20 gpurun_out/rehearse_sharded.log; exit 1; }
 SACENV_BENCH_BACKEND=gloo SACENV_BENCH_ONE_DEVICE=1 timeout -k 10 400 python -m torch.distributed.run \
-  --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 \
+  --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 \
   --envs 65536 --pooling gather --steps 256 --warmup 128 > gpurun_out/rehearse_gather.json \
   2> gpurun_out/rehearse_gather.log || { tail -20 gpurun_out/rehearse_gather.log; exit 1; }
 python - <<'PY'

@@ -11,14 +11,16 @@ rc=$?
 tail -5 gpurun_out/pytest_gpu.log
 [ $rc -eq 0 ] || { grep -E "FAIL|Error|error" gpurun_out/pytest_gpu.log | head -30; exit $rc; }
 [ -n "$SKIP_BENCH" ] && exit 0
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_driver.json \
-  2> gpurun_out/bench_driver.log || { tail -20 gpurun_out/bench_driver.log; exit 1; }
-timeout -k 10 300 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.log \
-  || { tail -20 gpurun_out/bench_default.log; exit 1; }
+export BENCH_OUT=${BENCH_OUT:-bench_out}   # the two bench lines (--full: roofline, cpu_baseline) land here
+mkdir -p "$BENCH_OUT"
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$BENCH_OUT/bench_driver.json" \
+  2> "$BENCH_OUT/bench_driver.log" || { tail -20 "$BENCH_OUT/bench_driver.log"; exit 1; }
+timeout -k 10 300 python bench.py --full > "$BENCH_OUT/bench_default.json" 2> "$BENCH_OUT/bench_default.log" \
+  || { tail -20 "$BENCH_OUT/bench_default.log"; exit 1; }
 python - <<'PY'
-import json
+import json, os
 for f in ("driver", "default"):
-    d = json.load(open(f"gpurun_out/bench_{f}.json"))
+    d = json.load(open(os.path.join(os.environ["BENCH_OUT"], f"bench_{f}.json")))
     r, c = d["roofline"], d["cpu_baseline"]
     print(f, f"{d['value']/1e9:.3f} G/s", f"{d['ms_per_step']*1e3:.2f} us/step", f"kernel {r.get('kernel_avg_us')} us",
           f"frac {r['frac']:.3f}", "cpu", c and round(c["value"]), c and c["cores"], c and round(c["one_core"]))

@@ -23,9 +23,9 @@ MODE=${PMC_KERNEL:-segment}
 if [ "$MODE" = step ]; then LAUNCH="--launch step"; PMCL="--launch step --no-graph"
 elif [ "$MODE" = rollout ]; then LAUNCH="--rollout 256"; PMCL="--rollout 256"
 else LAUNCH=""; PMCL=""; fi
-BENCH="python3 bench.py --steps ${PMC_STEPS:-256} --warmup 128 --no-cpu-baseline --no-every-output $PMCL"
+BENCH="python3 bench.py --full --steps ${PMC_STEPS:-256} --warmup 128 --no-cpu-baseline --no-every-output $PMCL"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_trace" -o run --output-format csv \
-  -- python3 bench.py --no-cpu-baseline --no-every-output $LAUNCH > "$OUT/prof_trace_bench.json" 2> "$OUT/prof_trace.log" || exit 1
+  -- python3 bench.py --full --no-cpu-baseline --no-every-output $LAUNCH > "$OUT/prof_trace_bench.json" 2> "$OUT/prof_trace.log" || exit 1
 i=0
 while read -r c; do
   i=$((i+1))

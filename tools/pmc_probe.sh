@@ -13,7 +13,7 @@ for w in "" "--test-mode 1 --episode-steps 0"; do
            "SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_SMEM"; do
     j=$((j+1))
     timeout -k 10 300 rocprofv3 --pmc $c -d "$OUT/w${i}_p$j" -o run --output-format csv \
-      -- python3 bench.py --steps 200 --warmup 100 --no-cpu-baseline --no-graph $w > /dev/null 2> "$OUT/w${i}_p$j.log" || exit 1
+      -- python3 bench.py --full --steps 200 --warmup 100 --no-cpu-baseline --no-graph $w > /dev/null 2> "$OUT/w${i}_p$j.log" || exit 1
   done
 done
 python3 - <<'PY'

@@ -6,7 +6,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p "$OUT"
-BENCH="python3 bench.py --steps 256 --warmup 128 --no-cpu-baseline --no-graph"
+BENCH="python3 bench.py --full --steps 256 --warmup 128 --no-cpu-baseline --no-graph"
 i=0
 while read -r c; do
   i=$((i+1))
