@@ -502,9 +502,11 @@ __device__ __forceinline__ SinCos sincos_ocml(double x) {
 __device__ __forceinline__ void sincos_cw(double x, double* sp, double* cp, const TrigK& K) {
   sincos_fast(x, sp, cp, K);
   const bool ok = fabs(x) <= kCwBound;
-  if (__ballot(!ok) != 0ull && !ok) {
-    const SinCos r = sincos_ocml(x);
-    *sp = r.s, *cp = r.c;
+  if (__builtin_expect(__ballot(!ok) != 0ull, 0)) {  // (unlikely: laid out off the step's fall-through path)
+    if (!ok) {
+      const SinCos r = sincos_ocml(x);
+      *sp = r.s, *cp = r.c;
+    }
   }
 }
 
@@ -537,7 +539,7 @@ __device__ __forceinline__ void trig3(double j, double r, double w, double* sj, 
   *sr = fma(r * zr, qr, r);
   sincos_quadrant(rw, zw, ps, pc, kw, sw, cw);
   const bool okj = fabs(j) <= kSinBound, okr = fabs(r) <= kSinBound, okw = fabs(w) <= kCwBound;
-  if (__ballot(!(okj && okr && okw)) != 0ull) {
+  if (__builtin_expect(__ballot(!(okj && okr && okw)) != 0ull, 0)) {
     if (!okj) *sj = sin_ocml(j);
     if (!okr) *sr = sin_ocml(r);
     if (!okw) {
@@ -1947,7 +1949,13 @@ __device__ uint32_t wait_flag(const uint32_t* f, uint32_t want, uint32_t seen, i
 // kHand (kRoll only): rows published step by step and/or done flags (the
 // closed loop); without it the loop carries no flag code at all (the launch
 // checked that every row was already published).
-template <bool kRoll, int kNc, bool kTIdx, bool kHand = false, int kRows = 1, bool kVc = kRoll>
+// kLean (kRoll only): the launch's options as the persistent segment of a
+// training loop has them, checked by the host dispatch (lean_launch): no
+// optional outputs (out_flags == 0), autoreset on, experiment != 2,
+// fuel0 != 0, and every step's record and terminal obs at the same address
+// (rec_stride == fin_stride == 0). The step loop then carries no test of
+// them and no code of the excluded cases.
+template <bool kRoll, int kNc, bool kTIdx, bool kHand = false, int kRows = 1, bool kVc = kRoll, bool kLean = false>
 __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Arena& A, const Tail& Tin,
                                            const float* __restrict__ action, OwnerLds& l, int ob,
                                            int lane, int n_steps = 1, const RollArgs* ra = nullptr,
@@ -1967,6 +1975,11 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   do {                 \
   } while (0)
 #endif
+  static_assert(!kLean || kRoll, "the lean options describe a multi-step launch");
+  const bool autoreset = kLean || pin.autoreset != 0;
+  const bool exp2 = !kLean && pin.experiment == 2;
+  const bool no_fuel = !kLean && pin.fuel0 == 0;
+  const uint32_t out_flags = kLean ? 0u : (uint32_t)pin.out_flags;
   const int e = ob * kWave + lane;
   const uint32_t eo = (uint32_t)e * 8u, eo4 = (uint32_t)e * 4u;  // per-lane byte offsets
   const char* const wbase = A.wk_wave(ob * kWave);  // the wave's slot-ring block (uniform)
@@ -1993,7 +2006,7 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   // 512-B rows; the wind piece and index first, as the wind is evaluated
   // first (measured 0.16 us/step faster than 16-B loads staged through LDS)
   int32_t index = A.i32e(U_IDX, eo4);
-  int cons = pin.autoreset ? A.i32e(U_CONS, eo4) : 0;  // (early: the refresh gathers' slot)
+  int cons = autoreset ? A.i32e(U_CONS, eo4) : 0;  // (early: the refresh gathers' slot)
   double cf[kCoef];
 #pragma unroll
   for (int k = 0; k < kCoef; ++k) cf[k] = 0.0;
@@ -2040,11 +2053,11 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   // rollout: the next pre-drawn episode's y(0) and start y, carried in registers
   double y0c[2] = {0.0, 0.0};
   int32_t syc = 0;
-  if (kRoll && p.autoreset) {
+  if (kRoll && autoreset) {
 #pragma unroll
     for (int c = 0; c < 2; ++c)
       if (c < nc) y0c[c] = A.f64e(U_W0N + 8 * c, eo);
-    if (p.experiment == 2) syc = A.i32e(U_SYN, eo4);
+    if (exp2) syc = A.i32e(U_SYN, eo4);
   }
 #ifdef SACENV_STAMPS
   // per-phase shader-clock sums over a launch's steps (tools/phase_stamps.py):
@@ -2133,7 +2146,7 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   const int wi = index > p.wind_len - 1 ? p.wind_len - 1 : index;
   Knot knext = kcur;
   double wv = 0.0, wa = 0.0;
-  bool refresh = false;
+  bool refresh = false, any_refresh = false;
   int jn = 0;
   double rq[kCoef];  // refreshed piece (refresh lanes), stored at the end
   if (nc == 0) {
@@ -2156,7 +2169,8 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
     jn = knext.j;
     refresh = index == 0 || jn != kcur.j;
     // (one wave-uniform branch: in ~3 of 4 steps no lane of the wave refreshes)
-    if (__ballot(refresh) != 0ull) {  // the piece of the next step's interval for refreshing lanes, stored at
+    any_refresh = __builtin_expect(__ballot(refresh) != 0ull, 0);
+    if (any_refresh) {  // the piece of the next step's interval for refreshing lanes, stored at
       // the end (own registers, read only there). Unconditional loads, the
       // other lanes reading one fixed line: with no branch around them the
       // waitcnt pass can count the loads in flight (a load under a divergent
@@ -2172,13 +2186,20 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   }
   // autoreset: the next pre-drawn episode's curve values at grid index 0 and
   // start y. Lanes in an episode's first step gather them from the slot ring
-  // and refresh their lane-coalesced copies; the others read the copies. One
-  // unconditional load per value from a per-lane address (no branch: see the
-  // refresh loads above; no select between two loaded registers either).
+  // and refresh their lane-coalesced copies; the others read the copies. The
+  // one-step launch: one unconditional load per value from a per-lane address
+  // (no divergent branch: see the refresh loads above; no select between two
+  // loaded registers either).
   double y0n[2];
   int32_t syn = 0;
-  const bool hdr_refresh = p.autoreset && index == 0;
-  {
+  const bool hdr_refresh = autoreset && index == 0;
+  // (multi-step loop: the copies are in registers, and only a step with a lane in
+  // its episode's first step -- the step after a restart -- gathers: one wave-uniform
+  // branch, off the common path, around the gathers)
+#pragma unroll
+  for (int c = 0; c < 2; ++c) y0n[c] = y0c[c];
+  if (kRoll) syn = syc;
+  if (!kRoll || __builtin_expect(__ballot(hdr_refresh) != 0ull, 0)) {
     const int ns = nslot;  // (cons + 1) % kSlots
 #pragma unroll
     for (int c = 0; c < 2; ++c)
@@ -2188,7 +2209,7 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
                                        : (kRoll ? A.wind_knots() : &A.f64e(U_W0N + 8 * c, eo)));
         y0n[c] = kRoll && !hdr_refresh ? y0c[c] : v;
       }
-    if (nc == 0 && p.experiment == 2) {
+    if (nc == 0 && exp2) {
       const int32_t v = *(hdr_refresh ? &A.i32e(U_STARTY + 4 * ns, eo4) : &A.i32e(U_SYN, eo4));
       syn = kRoll && !hdr_refresh ? syc : v;
     }
@@ -2275,7 +2296,8 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   ep = ep + reward;
   uint8_t term = active ? (uint8_t)tm : (uint8_t)SACENV_TERM_NONE;  // padding lanes never end
 
-  if (term != SACENV_TERM_NONE)  // no-return atomic: nothing on the critical path waits
+  // (the multi-step loop counts in its episode-end region, below)
+  if (!kRoll && term != SACENV_TERM_NONE)  // no-return atomic: nothing on the critical path waits
     __hip_atomic_fetch_add(&A.at_e<uint32_t>(U_CNT + 4 * (term - 1), eo4), 1u, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
   if (term == SACENV_TERM_NONE && active && p.max_episode_steps > 0 && index >= p.max_episode_steps)
@@ -2286,25 +2308,29 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
 
   OWNER_STAMP(st_computed);
   // this step's outputs: the arena's record, or the multi-step launch's
-  char* const R = kRoll ? ra->rec + (int64_t)ks * ra->rec_stride : A.b + A.ur() * A.np;
-  float* const fin = kRoll ? (ra->fin != nullptr ? ra->fin + (int64_t)ks * ra->fin_stride : nullptr)
-                           : A.final_obs();
+  // (kLean: both strides are 0, the addresses loop invariants)
+  char* const R = kLean ? ra->rec : kRoll ? ra->rec + (int64_t)ks * ra->rec_stride : A.b + A.ur() * A.np;
+  float* const fin = kLean   ? ra->fin
+                     : kRoll ? (ra->fin != nullptr ? ra->fin + (int64_t)ks * ra->fin_stride : nullptr)
+                             : A.final_obs();
   // (kRoll: kRows compiles the pooled row in or out; the step launch decides at run time)
   char* const trans = kRows != 1 ? nullptr
                               : kRoll ? (ra->trans != nullptr ? ra->trans + (int64_t)ks * ra->trans_stride : nullptr)
                                       : trans1;
-  if (p.out_flags & SACENV_OUT_REWARD64) A.at_e<double>(A.ur() + 126, eo) = reward;
-  if (p.out_flags & SACENV_OUT_ACCEL) {
+  if (out_flags & SACENV_OUT_REWARD64) A.at_e<double>(A.ur() + 126, eo) = reward;
+  if (out_flags & SACENV_OUT_ACCEL) {
     A.at_e<double>(A.ur() + 102, eo) = a_x;
     A.at_e<double>(A.ur() + 110, eo) = a_y;
     A.at_e<double>(A.ur() + 118, eo) = a_r;
   }
-  const bool restart = ended && p.autoreset;
-  if (ended) A.at_e<double>(A.ur() + 94, eo) = ep;
+  const bool restart = ended && autoreset;
   // terminal obs of the envs that auto-reset (main.py:72 reset, boat_env.py:121):
   // per-lane stores (measured 0.13 us/step cheaper than a 2.8-KB block store per
   // restarting wave with two extra barriers)
-  if (restart && fin != nullptr) store_obs(fin + (int64_t)e * SACENV_OBS_DIM, o);
+  if (!kRoll) {  // (the multi-step loop: in its episode-end region, below)
+    if (ended) A.at_e<double>(A.ur() + 94, eo) = ep;
+    if (restart && fin != nullptr) store_obs(fin + (int64_t)e * SACENV_OBS_DIM, o);
+  }
   int cons_out = cons;
   // the record's obs row: this step's obs, or a restarting lane's first obs of
   // its next episode. The restart's ~45 per-lane selects (state, row, slot ring)
@@ -2341,15 +2367,28 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
 #pragma unroll
   for (int k = 0; k < SACENV_OBS_DIM; ++k) row[k] = o.v[k];
   float row3_new = 0.0f;  // (exp 2's pooled row: the new episode's obs[3])
-  const bool any_restart = __ballot(restart) != 0ull;
-  if (any_restart) {
+  // The multi-step loop's episode-end region: everything a step does only for
+  // lanes whose episode ended (the termination counter, ep_reward, the terminal
+  // obs, the restart) behind ONE wave-uniform branch, the per-lane predicates
+  // inside it. In ~3 of 4 steps no lane of the wave ends, and the step falls
+  // through. (After the staged row's stores: a restarting lane's obs3_next
+  // lands in the row just stored, and the later store wins.)
+  // (the one-step launch: the restart's selects behind its own uniform branch, as before)
+  if (kRoll ? __builtin_expect(__ballot(ended) != 0ull, 0) : __ballot(restart) != 0ull) {
+    if (kRoll) {
+      if ((uint32_t)term - 1u < 5u)  // codes 1..5 (no-return atomic: nothing waits for it)
+        __hip_atomic_fetch_add(&A.at_e<uint32_t>(U_CNT + 4 * (term - 1), eo4), 1u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+      if (ended) A.at_e<double>(A.ur() + 94, eo) = ep;
+      if (restart && fin != nullptr) store_obs(fin + (int64_t)e * SACENV_OBS_DIM, o);
+    }
     if (restart) {  // next episode from its pre-drawn slot: a fresh Boat (boat_env.py:152-198)
-      const double sy0 = p.experiment == 2 ? (double)syn : 0.0;  // :166-169
+      const double sy0 = exp2 ? (double)syn : 0.0;  // :166-169
       s_x = 0.0, s_y = sy0, s_r = 0.0, v_x = 0.0, v_y = 0.0, v_r = 0.0, rudder = 0.0;
       t = 0.0, ep = 0.0;  // :122
       index = 0;
       Obs fo;
-      if (p.experiment == 2 || p.fuel0 == 0) {
+      if (exp2 || no_fuel) {
         fo = make_obs(p, oc, 0.0, 0.0, 0.0, sy0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, (double)p.fuel0);
       } else {  // make_obs of the zero state, folded: (0+W)/(2W) = 0.5 and fuel0/fuel0 = 1 exactly
         constexpr float kRud0 = (float)((0.0 + kPi / 3) * (1.0 / (kPi / 3 - (-kPi / 3))));
@@ -2362,9 +2401,18 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
 #pragma unroll
       for (int k = 0; k < SACENV_OBS_DIM; ++k) row[k] = fo.v[k];
       row3_new = fo.v[3];
-      if (kRoll && kRows == 2 && p.experiment == 2 && staged)  // the staged row's obs3_next
+      if (kRoll && kRows == 2 && exp2 && staged)  // the staged row's obs3_next
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(row3_new), srs, s_lane + 56u, (uint32_t)ks * 64u, 0);
       cons_out = cons + 1;
+      if (kRoll) {  // the next slot becomes current; grid index 0 (registers: no store)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+          if (c < nc) cf[4 * c] = y0n[c];
+        so = sno;
+        nslot = nslot + 1 == kSlots ? 0 : nslot + 1;
+        sno = nslot == 0 ? lane_ring : sno + slot_bytes;
+        knext = knot_coord(p, 0);
+      }
     }
   }
   // the dynamics' fields went out as they were computed; what is left: the
@@ -2395,27 +2443,20 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
 #pragma unroll
       for (int c = 0; c < 2; ++c)
         if (c < nc) st_out(A.f64e(U_W0N + 8 * c, eo), y0n[c]);
-      if (p.experiment == 2) st_out(A.i32e(U_SYN, eo4), syn);
+      if (exp2) st_out(A.i32e(U_SYN, eo4), syn);
     }
   } else {  // the same updates, in registers (each behind a wave-uniform branch)
-    if (nc > 0 && __ballot(refresh && !restart) != 0ull && refresh && !restart) {
+    if (nc > 0 && any_refresh) {  // (the branch of the loads above)
+      if (refresh && !restart) {
 #pragma unroll
-      for (int k = 0; k < kCoef; ++k) cf[k] = rq[k];
+        for (int k = 0; k < kCoef; ++k) cf[k] = rq[k];
+      }
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c) y0c[c] = y0n[c];
     syc = syn;
     cons = cons_out;
-    kcur = knext;
-    if (any_restart && restart) {  // the next slot becomes current; grid index 0
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-        if (c < nc) cf[4 * c] = y0n[c];
-      so = sno;
-      nslot = nslot + 1 == kSlots ? 0 : nslot + 1;
-      sno = nslot == 0 ? lane_ring : sno + slot_bytes;
-      kcur = knot_coord(p, 0);
-    }
+    kcur = knext;  // (a restarting lane's: grid index 0, set in the episode-end region)
   }
   if (kRows == 3) {  // (fresh rows: streaming stores, as the obs row below)
     __builtin_nontemporal_store((float)reward, reinterpret_cast<float*>(R + 44 * A.np + eo4));
@@ -2513,15 +2554,15 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
     A.f64e(U_EP, eo) = ep;
     A.i32e(U_IDX, eo4) = index;
     A.i32e(U_LTERM, eo4) = (int32_t)lt;
-    if (p.autoreset) A.i32e(U_CONS, eo4) = cons;
+    if (autoreset) A.i32e(U_CONS, eo4) = cons;
 #pragma unroll
     for (int k = 0; k < kCoef; ++k)
       if (k < 4 * nc) A.f64e(U_COEF + 8 * k, eo) = cf[k];
-    if (p.autoreset) {
+    if (autoreset) {
 #pragma unroll
       for (int c = 0; c < 2; ++c)
         if (c < nc) A.f64e(U_W0N + 8 * c, eo) = y0c[c];
-      if (p.experiment == 2) A.i32e(U_SYN, eo4) = syc;
+      if (exp2) A.i32e(U_SYN, eo4) = syc;
     }
   }
 
@@ -2579,7 +2620,9 @@ __global__ void __launch_bounds__(kWave) k_step(SacenvBoatParams p, Arena A, Tai
 // per SIMD, for grids with more owner waves than SIMDs -- 131 072 envs: 48.5
 // against 44.4 G env-steps/s; at one wave per SIMD the copies win, 1.34 against
 // 2.04 us per step). The same arithmetic either way: results are bit-identical.
-template <int kNc, bool kTIdx, int kRows, bool kVc>
+// kLean: the open loop with the launch's options compiled in (owner_wave); the
+// hand-off loop stays general.
+template <int kNc, bool kTIdx, int kRows, bool kVc, bool kLean>
 __device__ __forceinline__ void rollout_body(const SacenvBoatParams& p, const Arena& A, const Tail& T,
                                              const float* __restrict__ action, int n_steps, const RollArgs& ra,
                                              OwnerLds& slds) {
@@ -2618,29 +2661,29 @@ __device__ __forceinline__ void rollout_body(const SacenvBoatParams& p, const Ar
       owner_wave<true, kNc, kTIdx, true, kRows, false>(p, A, T, action, slds, ob, lane, n_steps, &ra, nullptr, seen);
   } else {
     if (kVc)
-      owner_wave<true, kNc, kTIdx, false, kRows, true>(vreg_params(p), A, vreg_tail(T), action, slds, ob, lane,
-                                                        n_steps, &ra);
+      owner_wave<true, kNc, kTIdx, false, kRows, true, kLean>(vreg_params(p), A, vreg_tail(T), action, slds, ob,
+                                                               lane, n_steps, &ra);
     else
-      owner_wave<true, kNc, kTIdx, false, kRows, false>(p, A, T, action, slds, ob, lane, n_steps, &ra);
+      owner_wave<true, kNc, kTIdx, false, kRows, false, kLean>(p, A, T, action, slds, ob, lane, n_steps, &ra);
   }
 }
-template <int kNc, bool kTIdx, int kRows>
+template <int kNc, bool kTIdx, int kRows, bool kLean = false>
 __global__ void __launch_bounds__(kWave) k_rollout(SacenvBoatParams p, Arena A, Tail T,
                                                    const float* __restrict__ action, int n_steps, RollArgs ra) {
   __shared__ OwnerLds slds;
-  rollout_body<kNc, kTIdx, kRows, true>(p, A, T, action, n_steps, ra, slds);
+  rollout_body<kNc, kTIdx, kRows, true, kLean>(p, A, T, action, n_steps, ra, slds);
 }
-template <int kNc, bool kTIdx, int kRows>
+template <int kNc, bool kTIdx, int kRows, bool kLean = false>
 __global__ void __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_rollout_dense(SacenvBoatParams p, Arena A, Tail T, const float* __restrict__ action, int n_steps, RollArgs ra) {
   __shared__ OwnerLds slds;
-  rollout_body<kNc, kTIdx, kRows, false>(p, A, T, action, n_steps, ra, slds);
+  rollout_body<kNc, kTIdx, kRows, false, kLean>(p, A, T, action, n_steps, ra, slds);
 }
 
 // sacenv_mixed_segment (BASELINE configs[4] as one persistent launch): the
 // boat's owner waves (k_rollout's open loop) and each toy arena's waves,
 // heterogeneous workgroups selected by uniform block-index ranges
-template <int kNc, bool kTIdx>
+template <int kNc, bool kTIdx, bool kLean = false>
 __global__ void __launch_bounds__(kWave) k_rollout_mixed(SacenvBoatParams p, Arena A, Tail T,
                                                          const float* __restrict__ action, int n_steps, RollArgs ra,
                                                          int nb_boat, MixedToys M) {
@@ -2648,8 +2691,8 @@ __global__ void __launch_bounds__(kWave) k_rollout_mixed(SacenvBoatParams p, Are
   const int lane = threadIdx.x;
   int b = (int)blockIdx.x;
   if (b < nb_boat) {
-    owner_wave<true, kNc, kTIdx, false, 0>(vreg_params(p), A, vreg_tail(T), action, slds, b, lane, n_steps,
-                                               &ra);
+    owner_wave<true, kNc, kTIdx, false, 0, true, kLean>(vreg_params(p), A, vreg_tail(T), action, slds, b, lane,
+                                                         n_steps, &ra);
     return;
   }
   b -= nb_boat;
@@ -2924,12 +2967,25 @@ static bool dense_grid(int nb_boat) {
   return nb_boat > 4 * cus;
 }
 
+// The lean instantiation's conditions (owner_wave's kLean), all of them: the
+// persistent segment of a training loop. Any other launch takes the general one.
+static bool lean_launch(const SacenvBoatParams& p, const RollArgs& ra) {
+  return p.out_flags == 0 && p.autoreset != 0 && p.experiment != 2 && p.fuel0 != 0 && ra.rec_stride == 0 &&
+         ra.fin_stride == 0;
+}
+
 static int launch_multi(const SacenvBoatParams& p, void* arena, const float* actions, int n_steps, const RollArgs& ra,
                         void* stream) {
   const int nb_boat = (int)(pad64(p.n_envs) / kWave);
   const bool dense = dense_grid(nb_boat);
+  const bool lean = lean_launch(p, ra);
+  // (lean: the staged rows and the plain record in place; the pooled rows and the
+  // fresh rows of sacenv_boat_rollout stay general)
 #define SACENV_LAUNCH_K(KER, NC, TI)                                                                       \
-  if (ra.stage != nullptr)                                                                                 \
+  if (ra.stage != nullptr && lean)                                                                         \
+    hipLaunchKernelGGL((KER<NC, TI, 2, true>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,      \
+                       make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
+  else if (ra.stage != nullptr)                                                                            \
     hipLaunchKernelGGL((KER<NC, TI, 2>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,            \
                        make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
   else if (ra.trans != nullptr)                                                                            \
@@ -2937,6 +2993,9 @@ static int launch_multi(const SacenvBoatParams& p, void* arena, const float* act
                        make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
   else if (ra.rec_stride != 0)                                                                             \
     hipLaunchKernelGGL((KER<NC, TI, 3>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,            \
+                       make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
+  else if (lean)                                                                                           \
+    hipLaunchKernelGGL((KER<NC, TI, 0, true>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,      \
                        make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
   else                                                                                                     \
     hipLaunchKernelGGL((KER<NC, TI, 0>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,            \
@@ -3030,8 +3089,16 @@ int sacenv_boat_segment_occupancy(const SacenvBoatParams* p, int32_t with_trans,
   hipError_t e = hipSuccess;
   hipFuncAttributes fa{};
   const bool dense = dense_grid((int)(pad64(p->n_envs) / kWave));  // the kernel launch_multi would pick
+  const bool lean = lean_launch(*p, RollArgs{});                   // (the segment's strides are 0)
+#define SACENV_OCC_ONE(K)                                                        \
+  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K, kWave, 0);            \
+  if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(K))
 #define SACENV_OCC_K(KER, NC, TI)                                                                            \
-  if (with_trans == 2) {                                                                                     \
+  if (with_trans == 2 && lean) {                                                                             \
+    SACENV_OCC_ONE((KER<NC, TI, 2, true>));                                                                  \
+  } else if (with_trans == 0 && lean) {                                                                      \
+    SACENV_OCC_ONE((KER<NC, TI, 0, true>));                                                                  \
+  } else if (with_trans == 2) {                                                                              \
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KER<NC, TI, 2>, kWave, 0);                         \
     if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(KER<NC, TI, 2>));       \
   } else if (with_trans) {                                                                                   \
@@ -3050,6 +3117,7 @@ int sacenv_boat_segment_occupancy(const SacenvBoatParams* p, int32_t with_trans,
   SACENV_OWNER_DISPATCH(*p, SACENV_OCC)
 #undef SACENV_OCC
 #undef SACENV_OCC_K
+#undef SACENV_OCC_ONE
   if (e != hipSuccess) return (int)e;
   *blocks_per_cu = nb;
   *grid = (int32_t)(pad64(p->n_envs) / kWave);
@@ -3221,9 +3289,15 @@ int sacenv_mixed_segment(const SacenvBoatParams* bp, void* boat_arena, const flo
     nb += nb_boat;
   }
   if (nb == 0) return SACENV_OK;
+  // (no boat: p is zeroed and no owner wave runs; the general instantiation)
+  const bool lean = lean_launch(p, ra);
 #define SACENV_LAUNCH(NC, TI)                                                                                  \
-  hipLaunchKernelGGL((k_rollout_mixed<NC, TI>), dim3(nb), dim3(kWave), 0, (hipStream_t)stream, p, A, T,        \
-                     boat_actions, n_steps, ra, nb_boat, M)
+  if (lean)                                                                                                    \
+    hipLaunchKernelGGL((k_rollout_mixed<NC, TI, true>), dim3(nb), dim3(kWave), 0, (hipStream_t)stream, p, A,   \
+                       T, boat_actions, n_steps, ra, nb_boat, M);                                              \
+  else                                                                                                         \
+    hipLaunchKernelGGL((k_rollout_mixed<NC, TI>), dim3(nb), dim3(kWave), 0, (hipStream_t)stream, p, A, T,      \
+                       boat_actions, n_steps, ra, nb_boat, M)
   SACENV_OWNER_DISPATCH(p, SACENV_LAUNCH)
 #undef SACENV_LAUNCH
   return launch_status();

@@ -1,4 +1,6 @@
-"""Instruction mix of the bench's segment-kernel loop (k_rollout<2, true, false>).
+"""Instruction mix of the bench's segment-kernel loop (k_rollout<2, true, 0, true>,
+the lean instantiation; --kernel SUBSTRING of the mangled name picks another, e.g.
+k_rolloutILi2ELb1ELi0ELb0EE, the general one).
 
 Compiles sacenv_boat.hip to gfx950 assembly (or reads --asm FILE), takes the
 kernel's open-loop body (the back-edge span that contains no flag spin) and
@@ -28,7 +30,7 @@ def asm_text(src=None):
     return open(out).read()
 
 
-def kernel(text, name="k_rolloutILi2ELb1ELi0E"):
+def kernel(text, name="k_rolloutILi2ELb1ELi0ELb1EE"):
     lines = text.split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*%s\w*:" % name, l))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
@@ -45,6 +47,20 @@ def loops(lines):
     return out
 
 
+def open_loop(k):
+    """The open loop's fall-through body: from the loop header to its own back edge.
+    Cold regions laid out behind the loop (the large-argument sincos, the
+    episode-end region) branch back into the body and look like longer loops:
+    the step counter's back edge is the scalar-condition one (s_cmp + s_cbranch_scc);
+    a plain s_branch to the label next to the header closes the same loop."""
+    cands = [(a, b) for a, b in loops(k) if b - a > 300 and not any("s_sleep" in x for x in k[a:b])]
+    scc = [ab for ab in cands if "s_cbranch_scc" in k[ab[1]]]
+    if not scc:  # the counter's test folded into a vector condition: the longest span, as before
+        return max(cands, key=lambda ab: ab[1] - ab[0])
+    a, b = min(scc, key=lambda ab: ab[1] - ab[0])
+    return a, max(b2 for a2, b2 in cands if a <= a2 <= a + 4 and b2 <= b + 4)
+
+
 def hist(body):
     c = collections.Counter()
     for l in body:
@@ -57,11 +73,10 @@ def hist(body):
 
 def main():
     text = open(sys.argv[sys.argv.index("--asm") + 1]).read() if "--asm" in sys.argv else asm_text()
-    k = kernel(text)
+    k = kernel(text, sys.argv[sys.argv.index("--kernel") + 1]) if "--kernel" in sys.argv else kernel(text)
     meta = [l.strip() for l in text.split("\n") if re.search(r"\.(vgpr|sgpr|agpr)_count|vgpr_spill|sgpr_spill", l)]
     # outermost loops without a flag spin (s_sleep) = the open loop
-    cands = [(a, b) for a, b in loops(k) if b - a > 500 and not any("s_sleep" in x for x in k[a:b])]
-    a, b = max(cands, key=lambda ab: ab[1] - ab[0])
+    a, b = open_loop(k)
     h = hist(k[a:b + 1])
     cls = collections.Counter()
     for op, n in h.items():
