@@ -43,6 +43,11 @@ extern "C" {
 #define SACENV_SLOTS 257       /* episode slots per env in autoreset mode (active + 256 ahead) */
 #define SACENV_REFILL_PERIOD 256 /* autoreset: at most this many step launches between refills */
 #define SACENV_RECORD_BYTES 50 /* packed per-env step record (see layout.record) */
+/* the record's per-env byte columns: field f of n_pad envs starts at column x n_pad */
+#define SACENV_REC_OBS 0       /* f32 [n_pad][SACENV_OBS_DIM] */
+#define SACENV_REC_REWARD 44   /* f32 [n_pad]: 4 x SACENV_OBS_DIM */
+#define SACENV_REC_DONE 48     /* u8 [n_pad] */
+#define SACENV_REC_TERM 49     /* u8 [n_pad]; the record ends at SACENV_RECORD_BYTES */
 #define SACENV_TRANS_OBS 11     /* s' entries in the transition row (the whole obs) */
 #define SACENV_TRANS_BYTES 53   /* per-env transition row of sacenv_boat_step_pooled */
 #define SACENV_TRANS_BYTES_EXP2 57 /* the same in experiment 2 (+ obs3_next) */

@@ -77,9 +77,43 @@ constexpr int64_t kWindUnits = 16LL * kSlots;  // f64 x 2 curves x slots, per kn
 __host__ __device__ inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
 __host__ __device__ inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
+// The packed record's per-env byte columns (sacenv.h: what a step hands out, and
+// what sacenv_boat_rollout writes per step), then the columns that follow the
+// record in the arena: field f starts (record_unit + R_f) * n_pad bytes in.
+constexpr int R_OBS = SACENV_REC_OBS, R_REWARD = SACENV_REC_REWARD, R_DONE = SACENV_REC_DONE,
+              R_TERM = SACENV_REC_TERM, R_FIN = SACENV_RECORD_BYTES,  // final_obs: f32 [n_pad][11]
+              R_FIN_EP = R_FIN + 4 * SACENV_OBS_DIM,                   // final_ep_reward: f64
+              R_AX = R_FIN_EP + 8, R_AY = R_AX + 8, R_AR = R_AY + 8,   // accel: f64 [3][n_pad]
+              R_REWARD64 = R_AR + 8, R_END = R_REWARD64 + 8;
+static_assert(R_OBS == 0 && R_REWARD == 4 * SACENV_OBS_DIM && R_DONE == R_REWARD + 4 && R_TERM == R_DONE + 1 &&
+                  SACENV_RECORD_BYTES == R_TERM + 1,
+              "record: obs f32 x 11, reward f32, done u8, term u8");
+static_assert(R_FIN == 50 && R_FIN_EP == 94 && R_AX == 102 && R_AY == 110 && R_AR == 118 && R_REWARD64 == 126 &&
+                  R_END == 134,
+              "the arena columns behind the record (SacenvBoatLayout, ABI 20)");
+static_assert(R_FIN_EP % 2 == 0 && (R_AX - R_FIN_EP) % 8 == 0, "f64 columns stay 8-B aligned (n_pad % 64 == 0)");
+
+// The record's unit offset (its byte offset / n_pad): behind the slot ring (with
+// the raw knots when SACENV_OUT_KNOTS keeps them) and the two MT blocks.
+__host__ __device__ inline int64_t record_unit(int nk, int rk) {
+  return U_WIND + (2 + rk) * (kWindUnits * nk) + 2 * U_MT_BYTES;
+}
+// Byte offsets of what follows the per-env fields, each 256-B aligned: the refill
+// masks (one 64-bit word per owner wave), the status words, the spline matrix and
+// the shared wind table.
+__host__ __device__ inline int64_t off_refill_mask(int64_t ur, int64_t np) { return align256((ur + R_END) * np); }
+__host__ __device__ inline int64_t refill_mask_bytes(int64_t np) { return align256(8 * (int)(np / 64)); }
+__host__ __device__ inline int64_t off_status(int64_t ur, int64_t np) {
+  return off_refill_mask(ur, np) + refill_mask_bytes(np);
+}
+__host__ __device__ inline int64_t off_spline_g(int64_t ur, int64_t np) { return off_status(ur, np) + 256; }
+__host__ __device__ inline int64_t off_wind_table(int64_t ur, int64_t np) {
+  return off_spline_g(ur, np) + align256(8LL * kMaxK * kMaxK);
+}
+
 __host__ __device__ inline void compute_layout(int n, int nk, int L, int use_table, int raw_knots,
                                                SacenvBoatLayout* o) {
-  const int64_t np = pad64(n), nw = np / 64;
+  const int64_t np = pad64(n);
   o->n_pad = np;
   // paired fields: the offset of env 0's element; consecutive envs are 16 B apart
   auto pair_off = [np](int u) { return (int64_t)(u & ~15) * np + (u & 8); };
@@ -109,26 +143,21 @@ __host__ __device__ inline void compute_layout(int n, int nk, int L, int use_tab
   o->knots_raw = raw_knots ? (uw + 2 * wk) * np : -1;
   o->mt_key = (uw + (2 + rk) * wk) * np;
   o->mt_next = o->mt_key + U_MT_BYTES * np;
-  const int64_t ur = uw + (2 + rk) * wk + 2 * U_MT_BYTES;
+  const int64_t ur = record_unit(nk, (int)rk);
   o->record = ur * np;
-  o->obs = ur * np;
-  o->reward = (ur + 44) * np;
-  o->done = (ur + 48) * np;
-  o->term = (ur + 49) * np;
-  o->final_obs = (ur + 50) * np;
-  o->final_ep_reward = (ur + 94) * np;
-  o->accel = (ur + 102) * np;
-  o->reward64 = (ur + 126) * np;
-  int64_t off = align256((ur + 134) * np);
-  o->refill_mask = off;
-  off += align256(8 * nw);
-  o->status = off;
-  off += 256;
-  o->spline_g = off;
-  off += align256(8LL * kMaxK * kMaxK);
-  o->wind_table = off;
-  off += use_table ? align256(16LL * L) : 0;
-  o->total_bytes = off;
+  o->obs = (ur + R_OBS) * np;
+  o->reward = (ur + R_REWARD) * np;
+  o->done = (ur + R_DONE) * np;
+  o->term = (ur + R_TERM) * np;
+  o->final_obs = (ur + R_FIN) * np;
+  o->final_ep_reward = (ur + R_FIN_EP) * np;
+  o->accel = (ur + R_AX) * np;
+  o->reward64 = (ur + R_REWARD64) * np;
+  o->refill_mask = off_refill_mask(ur, np);
+  o->status = off_status(ur, np);
+  o->spline_g = off_spline_g(ur, np);
+  o->wind_table = off_wind_table(ur, np);
+  o->total_bytes = o->wind_table + (use_table ? align256(16LL * L) : 0);
   o->last_term = U_LTERM * np;
 }
 
@@ -150,16 +179,16 @@ struct Arena {
   __device__ __forceinline__ double* knots_raw() const { return at<double>(U_WIND + 2 * wk()); }
   __device__ __forceinline__ uint32_t* mt_key() const { return at<uint32_t>(U_WIND + (2 + rk) * wk()); }
   __device__ __forceinline__ uint32_t* mt_next() const { return mt_key() + kMtN * np; }
-  __device__ __forceinline__ int64_t ur() const { return U_WIND + (2 + rk) * wk() + 2 * U_MT_BYTES; }
-  __device__ __forceinline__ float* obs() const { return at<float>(ur()); }
-  __device__ __forceinline__ float* reward() const { return at<float>(ur() + 44); }
-  __device__ __forceinline__ uint8_t* done() const { return at<uint8_t>(ur() + 48); }
-  __device__ __forceinline__ uint8_t* term() const { return at<uint8_t>(ur() + 49); }
-  __device__ __forceinline__ float* final_obs() const { return at<float>(ur() + 50); }
-  __device__ __forceinline__ double* final_ep() const { return at<double>(ur() + 94); }
-  __device__ __forceinline__ double* accel() const { return at<double>(ur() + 102); }
-  __device__ __forceinline__ double* reward64() const { return at<double>(ur() + 126); }
-  __device__ __forceinline__ char* tail() const { return b + align256((ur() + 134) * np); }
+  __host__ __device__ __forceinline__ int64_t ur() const { return record_unit(nk, rk); }
+  __device__ __forceinline__ float* obs() const { return at<float>(ur() + R_OBS); }
+  __device__ __forceinline__ float* reward() const { return at<float>(ur() + R_REWARD); }
+  __device__ __forceinline__ uint8_t* done() const { return at<uint8_t>(ur() + R_DONE); }
+  __device__ __forceinline__ uint8_t* term() const { return at<uint8_t>(ur() + R_TERM); }
+  __device__ __forceinline__ float* final_obs() const { return at<float>(ur() + R_FIN); }
+  __device__ __forceinline__ double* final_ep() const { return at<double>(ur() + R_FIN_EP); }
+  __device__ __forceinline__ double* accel() const { return at<double>(ur() + R_AX); }
+  __device__ __forceinline__ double* reward64() const { return at<double>(ur() + R_REWARD64); }
+  __device__ __forceinline__ char* tail() const { return b + off_refill_mask(ur(), np); }
   // envs of owner wave w that ended since the last refill
   __device__ __forceinline__ unsigned long long* refill_mask() const {
     return reinterpret_cast<unsigned long long*>(tail());
@@ -172,7 +201,7 @@ struct Arena {
   __device__ __forceinline__ int32_t* cons_snap() const { return i32(U_CSNAP); }
   // [0] refills done, [1] SACENV_STATUS_* bits, [2] envs ranked by the last refill
   __device__ __forceinline__ int32_t* status() const {
-    return reinterpret_cast<int32_t*>(tail() + align256(8 * nwaves()));
+    return reinterpret_cast<int32_t*>(tail() + refill_mask_bytes(np));  // (= b + off_status)
   }
   // refill rank -> [0] env, [1] first and [2] end episode number drawn
   __device__ __forceinline__ int32_t* refill_list(int k) const { return i32(U_LIST + 4 * k); }
@@ -985,9 +1014,9 @@ __device__ __forceinline__ Obs fresh_state(const SacenvBoatParams& p, const Aren
   A.f64e(U_EP, eo) = 0.0;  // :122
   A.i32(U_IDX)[e] = 0;
   if (p.out_flags & SACENV_OUT_ACCEL) {  // a fresh Boat's a_x, a_y, a_r are 0 (:182-196)
-    A.at_e<double>(A.ur() + 102, eo) = 0.0;
-    A.at_e<double>(A.ur() + 110, eo) = 0.0;
-    A.at_e<double>(A.ur() + 118, eo) = 0.0;
+    A.at_e<double>(A.ur() + R_AX, eo) = 0.0;
+    A.at_e<double>(A.ur() + R_AY, eo) = 0.0;
+    A.at_e<double>(A.ur() + R_AR, eo) = 0.0;
   }
   return make_obs(p, obs_const(T), 0.0, 0.0, 0.0, s_y, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, (double)p.fuel0);
 }
@@ -2317,18 +2346,18 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   char* const trans = kRows != 1 ? nullptr
                               : kRoll ? (ra->trans != nullptr ? ra->trans + (int64_t)ks * ra->trans_stride : nullptr)
                                       : trans1;
-  if (out_flags & SACENV_OUT_REWARD64) A.at_e<double>(A.ur() + 126, eo) = reward;
+  if (out_flags & SACENV_OUT_REWARD64) A.at_e<double>(A.ur() + R_REWARD64, eo) = reward;
   if (out_flags & SACENV_OUT_ACCEL) {
-    A.at_e<double>(A.ur() + 102, eo) = a_x;
-    A.at_e<double>(A.ur() + 110, eo) = a_y;
-    A.at_e<double>(A.ur() + 118, eo) = a_r;
+    A.at_e<double>(A.ur() + R_AX, eo) = a_x;
+    A.at_e<double>(A.ur() + R_AY, eo) = a_y;
+    A.at_e<double>(A.ur() + R_AR, eo) = a_r;
   }
   const bool restart = ended && autoreset;
   // terminal obs of the envs that auto-reset (main.py:72 reset, boat_env.py:121):
   // per-lane stores (measured 0.13 us/step cheaper than a 2.8-KB block store per
   // restarting wave with two extra barriers)
   if (!kRoll) {  // (the multi-step loop: in its episode-end region, below)
-    if (ended) A.at_e<double>(A.ur() + 94, eo) = ep;
+    if (ended) A.at_e<double>(A.ur() + R_FIN_EP, eo) = ep;
     if (restart && fin != nullptr) store_obs(fin + (int64_t)e * SACENV_OBS_DIM, o);
   }
   int cons_out = cons;
@@ -2379,7 +2408,7 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
       if ((uint32_t)term - 1u < 5u)  // codes 1..5 (no-return atomic: nothing waits for it)
         __hip_atomic_fetch_add(&A.at_e<uint32_t>(U_CNT + 4 * (term - 1), eo4), 1u, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
-      if (ended) A.at_e<double>(A.ur() + 94, eo) = ep;
+      if (ended) A.at_e<double>(A.ur() + R_FIN_EP, eo) = ep;
       if (restart && fin != nullptr) store_obs(fin + (int64_t)e * SACENV_OBS_DIM, o);
     }
     if (restart) {  // next episode from its pre-drawn slot: a fresh Boat (boat_env.py:152-198)
@@ -2459,13 +2488,13 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
     kcur = knext;  // (a restarting lane's: grid index 0, set in the episode-end region)
   }
   if (kRows == 3) {  // (fresh rows: streaming stores, as the obs row below)
-    __builtin_nontemporal_store((float)reward, reinterpret_cast<float*>(R + 44 * A.np + eo4));
-    __builtin_nontemporal_store((uint8_t)(ended ? 1 : 0), reinterpret_cast<uint8_t*>(R + 48 * A.np + e));
-    __builtin_nontemporal_store(term, reinterpret_cast<uint8_t*>(R + 49 * A.np + e));
+    __builtin_nontemporal_store((float)reward, reinterpret_cast<float*>(R + R_REWARD * A.np + eo4));
+    __builtin_nontemporal_store((uint8_t)(ended ? 1 : 0), reinterpret_cast<uint8_t*>(R + R_DONE * A.np + e));
+    __builtin_nontemporal_store(term, reinterpret_cast<uint8_t*>(R + R_TERM * A.np + e));
   } else {
-    st_out<kWT>(*reinterpret_cast<float*>(R + 44 * A.np + eo4), (float)reward);
-    st_out<kWT>(*reinterpret_cast<uint8_t*>(R + 48 * A.np + e), (uint8_t)(ended ? 1 : 0));
-    st_out<kWT>(*reinterpret_cast<uint8_t*>(R + 49 * A.np + e), term);
+    st_out<kWT>(*reinterpret_cast<float*>(R + R_REWARD * A.np + eo4), (float)reward);
+    st_out<kWT>(*reinterpret_cast<uint8_t*>(R + R_DONE * A.np + e), (uint8_t)(ended ? 1 : 0));
+    st_out<kWT>(*reinterpret_cast<uint8_t*>(R + R_TERM * A.np + e), term);
   }
   // a restarting env's row is its new episode's first obs
   if (!kWT) {
@@ -2756,12 +2785,10 @@ int check_params(const SacenvBoatParams* p) {
 }
 
 Tail make_tail(const SacenvBoatParams& p, void* arena) {
-  SacenvBoatLayout L;
-  compute_layout(p.n_envs, p.n_knots, p.wind_len, p.use_wind_table, (p.out_flags & SACENV_OUT_KNOTS) != 0, &L);
-  char* b = static_cast<char*>(arena);
+  const Arena A = make_arena(p, arena);
   Tail T;
-  T.g = reinterpret_cast<const double*>(b + L.spline_g);
-  T.table = reinterpret_cast<const double*>(b + L.wind_table);
+  T.g = reinterpret_cast<const double*>(A.b + off_spline_g(A.ur(), A.np));
+  T.table = reinterpret_cast<const double*>(A.b + off_wind_table(A.ur(), A.np));
   T.r_mx = 1.0 / p.m_plus_mx;
   T.r_my = 1.0 / p.m_plus_my;
   T.r_iz = 1.0 / p.i_plus_iz;
@@ -2795,6 +2822,154 @@ int check_toy(const SacenvToyParams* p) {
 
 ToyArena make_toy_arena(const SacenvToyParams& p, void* base) {
   return ToyArena{static_cast<char*>(base), pad64(p.n_envs)};
+}
+
+// ---- kernel choice: every family's instantiation for a launch is picked here,
+// once; the entry points launch (or ask the runtime about) the pointer they get.
+using StepKernel = void (*)(SacenvBoatParams, Arena, Tail, const float*, int, MixedToys, char*);
+using RolloutKernel = void (*)(SacenvBoatParams, Arena, Tail, const float*, int, RollArgs);
+using MixedRolloutKernel = void (*)(SacenvBoatParams, Arena, Tail, const float*, int, RollArgs, int, MixedToys);
+using FitKernel = void (*)(SacenvBoatParams, Arena, Tail);
+
+// The step kernels' wind kind and t rule (owner_wave's template arguments): the
+// one switch over them; f gets them as Owner<kNc, kTIdx>.
+template <int kNc, bool kTIdx>
+struct Owner {
+  static constexpr int nc = kNc;
+  static constexpr bool ti = kTIdx;
+};
+int owner_curves(const SacenvBoatParams& p) { return p.use_wind_table ? 0 : n_curves(p.experiment); }
+template <class F>
+auto owner_dispatch(const SacenvBoatParams& p, F f) {
+  switch (owner_curves(p) * 2 + (t_from_index(p.dt) ? 1 : 0)) {
+    case 0: return f(Owner<0, false>{});
+    case 1: return f(Owner<0, true>{});
+    case 2: return f(Owner<1, false>{});
+    case 3: return f(Owner<1, true>{});
+    case 4: return f(Owner<2, false>{});
+    default: return f(Owner<2, true>{});
+  }
+}
+
+StepKernel step_kernel(const SacenvBoatParams& p, bool mixed) {
+  return owner_dispatch(p, [mixed](auto o) -> StepKernel {
+    using O = decltype(o);
+    return mixed ? k_step<true, O::nc, O::ti> : k_step<false, O::nc, O::ti>;
+  });
+}
+
+// More owner waves than the device has SIMDs: the two-waves-per-SIMD
+// instantiation (k_rollout_dense), which keeps every owner wave resident.
+bool dense_grid(int nb_boat) {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return false;
+  return nb_boat > 4 * cus;
+}
+
+// The lean instantiation's conditions (owner_wave's kLean), all of them: the
+// persistent segment of a training loop. Any other launch takes the general one.
+bool lean_launch(const SacenvBoatParams& p, const RollArgs& ra) {
+  return p.out_flags == 0 && p.autoreset != 0 && p.experiment != 2 && p.fuel0 != 0 && ra.rec_stride == 0 &&
+         ra.fin_stride == 0;
+}
+
+// The rows a multi-step launch writes besides the record (owner_wave's kRows):
+// 2 staged replay rows, 1 pooled rows, 3 a fresh record per step, 0 none.
+int rollout_rows(const RollArgs& ra) {
+  return ra.stage != nullptr ? 2 : ra.trans != nullptr ? 1 : ra.rec_stride != 0 ? 3 : 0;
+}
+
+template <int kNc, bool kTIdx, int kRows, bool kLean = false>
+RolloutKernel rollout_one(bool dense) {
+  return dense ? k_rollout_dense<kNc, kTIdx, kRows, kLean> : k_rollout<kNc, kTIdx, kRows, kLean>;
+}
+// k_rollout / k_rollout_dense for the launch: 6 owners x 6 (rows, lean) x 2. Lean
+// exists for the staged rows and the plain record in place (rows 2 and 0); the
+// pooled rows and the fresh rows of sacenv_boat_rollout stay general.
+RolloutKernel rollout_kernel(const SacenvBoatParams& p, int rows, bool lean, bool dense) {
+  return owner_dispatch(p, [=](auto o) -> RolloutKernel {
+    constexpr int nc = decltype(o)::nc;
+    constexpr bool ti = decltype(o)::ti;
+    switch (rows) {
+      case 0: return lean ? rollout_one<nc, ti, 0, true>(dense) : rollout_one<nc, ti, 0>(dense);
+      case 1: return rollout_one<nc, ti, 1>(dense);
+      case 2: return lean ? rollout_one<nc, ti, 2, true>(dense) : rollout_one<nc, ti, 2>(dense);
+      default: return rollout_one<nc, ti, 3>(dense);
+    }
+  });
+}
+
+MixedRolloutKernel rollout_mixed_kernel(const SacenvBoatParams& p, bool lean) {
+  return owner_dispatch(p, [lean](auto o) -> MixedRolloutKernel {
+    using O = decltype(o);
+    return lean ? k_rollout_mixed<O::nc, O::ti, true> : k_rollout_mixed<O::nc, O::ti>;
+  });
+}
+
+// the refill's fit: 8 or 16 knots per group, kFull when every one is used
+FitKernel refill_fit_kernel(int n_knots) {
+  return n_knots == 8   ? k_refill_fit<8, true>
+         : n_knots < 8  ? k_refill_fit<8, false>
+         : n_knots == 16 ? k_refill_fit<16, true>
+                         : k_refill_fit<16, false>;
+}
+
+// The RollArgs of a launch that writes the arena's own record every step: the
+// record, the terminal obs behind it (strides 0) and the hand-off status word.
+RollArgs arena_roll_args(const Arena& A) {
+  RollArgs ra{};
+  ra.rec = A.b + A.ur() * A.np;
+  ra.fin = reinterpret_cast<float*>(ra.rec + R_FIN * A.np);
+  ra.status = reinterpret_cast<int32_t*>(A.b + off_status(A.ur(), A.np)) + 1;
+  return ra;
+}
+
+int launch_multi(const SacenvBoatParams& p, void* arena, const float* actions, int n_steps, const RollArgs& ra,
+                 void* stream) {
+  const int nb_boat = (int)(pad64(p.n_envs) / kWave);
+  const RolloutKernel k = rollout_kernel(p, rollout_rows(ra), lean_launch(p, ra), dense_grid(nb_boat));
+  hipLaunchKernelGGL(k, dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p, make_arena(p, arena),
+                     make_tail(p, arena), actions, n_steps, ra);
+  return launch_status();
+}
+
+// A mixed launch's workgroups: the boat's owner waves (if any) first, then each
+// toy arena's waves.
+struct MixedLaunch {
+  MixedToys M{};
+  SacenvBoatParams p{};  // (no boat: zeroed, and no owner wave runs)
+  Arena A{};
+  Tail T{};
+  int nb_boat = 0, nb = 0;
+};
+int mixed_setup(const SacenvBoatParams* bp, void* boat_arena, const float* boat_actions,
+                const SacenvToyParams* toy_params, void* const* toy_arenas, int32_t n_toys, int32_t n_steps,
+                MixedLaunch* L) {
+  int rc;
+  if (n_toys < 0 || n_toys > 2) return SACENV_E_SIZE;
+  if (n_toys > 0 && (toy_params == nullptr || toy_arenas == nullptr)) return SACENV_E_NULL;
+  if (n_steps < 1) return SACENV_E_SIZE;
+  L->M.n = n_toys;
+  for (int t = 0; t < n_toys; ++t) {
+    if ((rc = check_toy(&toy_params[t]))) return rc;
+    if (toy_arenas[t] == nullptr) return SACENV_E_NULL;
+    L->M.p[t] = toy_params[t];
+    L->M.a[t] = make_toy_arena(toy_params[t], toy_arenas[t]);
+    L->M.nb[t] = blocks_for(toy_params[t].n_envs, kWave);
+    L->nb += L->M.nb[t];
+  }
+  if (bp != nullptr) {
+    if ((rc = check_params(bp))) return rc;
+    if (boat_arena == nullptr || boat_actions == nullptr) return SACENV_E_NULL;
+    L->p = *bp;
+    L->A = make_arena(*bp, boat_arena);
+    L->T = make_tail(*bp, boat_arena);
+    L->nb_boat = (int)(pad64(bp->n_envs) / kWave);
+    L->nb += L->nb_boat;
+  }
+  return SACENV_OK;
 }
 
 }  // namespace
@@ -2920,28 +3095,13 @@ int sacenv_boat_reset_explicit(const SacenvBoatParams* p, void* arena, const int
   return launch_status();
 }
 
-// the step kernels' wind kind and t rule (owner_wave's template arguments)
-static int owner_curves(const SacenvBoatParams& p) { return p.use_wind_table ? 0 : n_curves(p.experiment); }
-#define SACENV_OWNER_DISPATCH(p, LAUNCH)                                  \
-  switch (owner_curves(p) * 2 + (t_from_index((p).dt) ? 1 : 0)) {         \
-    case 0: LAUNCH(0, false); break;                                      \
-    case 1: LAUNCH(0, true); break;                                       \
-    case 2: LAUNCH(1, false); break;                                      \
-    case 3: LAUNCH(1, true); break;                                       \
-    case 4: LAUNCH(2, false); break;                                      \
-    default: LAUNCH(2, true); break;                                      \
-  }
-
 static int boat_step(const SacenvBoatParams* p, void* arena, const float* action, char* trans, void* stream) {
   int rc = check_params(p);
   if (rc) return rc;
   if (arena == nullptr || action == nullptr) return SACENV_E_NULL;
   const int nb_boat = (int)(pad64(p->n_envs) / kWave);
-#define SACENV_LAUNCH(NC, TI)                                                                         \
-  hipLaunchKernelGGL((k_step<false, NC, TI>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, *p, \
-                     make_arena(*p, arena), make_tail(*p, arena), action, nb_boat, MixedToys{}, trans)
-  SACENV_OWNER_DISPATCH(*p, SACENV_LAUNCH)
-#undef SACENV_LAUNCH
+  hipLaunchKernelGGL(step_kernel(*p, false), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, *p,
+                     make_arena(*p, arena), make_tail(*p, arena), action, nb_boat, MixedToys{}, trans);
   return launch_status();
 }
 
@@ -2956,74 +3116,6 @@ int sacenv_boat_step_pooled(const SacenvBoatParams* p, void* arena, const float*
   return boat_step(p, arena, action, static_cast<char*>(trans), stream);
 }
 
-// k_rollout for the launch's wind kind and t rule
-// More owner waves than the device has SIMDs: the two-waves-per-SIMD
-// instantiation (k_rollout_dense), which keeps every owner wave resident.
-static bool dense_grid(int nb_boat) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return false;
-  return nb_boat > 4 * cus;
-}
-
-// The lean instantiation's conditions (owner_wave's kLean), all of them: the
-// persistent segment of a training loop. Any other launch takes the general one.
-static bool lean_launch(const SacenvBoatParams& p, const RollArgs& ra) {
-  return p.out_flags == 0 && p.autoreset != 0 && p.experiment != 2 && p.fuel0 != 0 && ra.rec_stride == 0 &&
-         ra.fin_stride == 0;
-}
-
-static int launch_multi(const SacenvBoatParams& p, void* arena, const float* actions, int n_steps, const RollArgs& ra,
-                        void* stream) {
-  const int nb_boat = (int)(pad64(p.n_envs) / kWave);
-  const bool dense = dense_grid(nb_boat);
-  const bool lean = lean_launch(p, ra);
-  // (lean: the staged rows and the plain record in place; the pooled rows and the
-  // fresh rows of sacenv_boat_rollout stay general)
-#define SACENV_LAUNCH_K(KER, NC, TI)                                                                       \
-  if (ra.stage != nullptr && lean)                                                                         \
-    hipLaunchKernelGGL((KER<NC, TI, 2, true>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,      \
-                       make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
-  else if (ra.stage != nullptr)                                                                            \
-    hipLaunchKernelGGL((KER<NC, TI, 2>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,            \
-                       make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
-  else if (ra.trans != nullptr)                                                                            \
-    hipLaunchKernelGGL((KER<NC, TI, 1>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,            \
-                       make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
-  else if (ra.rec_stride != 0)                                                                             \
-    hipLaunchKernelGGL((KER<NC, TI, 3>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,            \
-                       make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
-  else if (lean)                                                                                           \
-    hipLaunchKernelGGL((KER<NC, TI, 0, true>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,      \
-                       make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra);                   \
-  else                                                                                                     \
-    hipLaunchKernelGGL((KER<NC, TI, 0>), dim3(nb_boat), dim3(kWave), 0, (hipStream_t)stream, p,            \
-                       make_arena(p, arena), make_tail(p, arena), actions, n_steps, ra)
-#define SACENV_LAUNCH(NC, TI)                  \
-  if (dense) {                                 \
-    SACENV_LAUNCH_K(k_rollout_dense, NC, TI);  \
-  } else {                                     \
-    SACENV_LAUNCH_K(k_rollout, NC, TI);        \
-  }
-  SACENV_OWNER_DISPATCH(p, SACENV_LAUNCH)
-#undef SACENV_LAUNCH
-#undef SACENV_LAUNCH_K
-  return launch_status();
-}
-
-// byte offsets of the record and the status words in the arena
-static int64_t A_ur_bytes(const SacenvBoatParams& p) {
-  SacenvBoatLayout L;
-  compute_layout(p.n_envs, p.n_knots, p.wind_len, p.use_wind_table, (p.out_flags & SACENV_OUT_KNOTS) != 0, &L);
-  return L.record;
-}
-static int64_t status_offset(const SacenvBoatParams& p) {
-  SacenvBoatLayout L;
-  compute_layout(p.n_envs, p.n_knots, p.wind_len, p.use_wind_table, (p.out_flags & SACENV_OUT_KNOTS) != 0, &L);
-  return L.status;
-}
-
 int sacenv_boat_rollout(const SacenvBoatParams* p, void* arena, const float* actions, int32_t n_steps,
                         void* records, float* final_obs, void* stream) {
   int rc = check_params(p);
@@ -3033,7 +3125,7 @@ int sacenv_boat_rollout(const SacenvBoatParams* p, void* arena, const float* act
   const int64_t np = pad64(p->n_envs);
   RollArgs ra{};
   ra.rec = static_cast<char*>(records);
-  ra.rec_stride = 50 * np;
+  ra.rec_stride = SACENV_RECORD_BYTES * np;
   ra.fin = final_obs;
   ra.fin_stride = np * SACENV_OBS_DIM;
   ra.act_stride = p->n_envs;
@@ -3058,12 +3150,7 @@ int sacenv_boat_segment(const SacenvBoatParams* p, void* arena, const float* act
   // the marks are staged into the wave's LDS (OwnerLds::mk: one word per step, REFILL_PERIOD
   // entries), whatever the autoreset setting
   if (stage_marks != nullptr && n_steps > SACENV_REFILL_PERIOD) return SACENV_E_SIZE;
-  const Arena A = make_arena(*p, arena);
-  RollArgs ra{};
-  ra.rec = static_cast<char*>(arena) + A_ur_bytes(*p);
-  ra.rec_stride = 0;
-  ra.fin = reinterpret_cast<float*>(static_cast<char*>(arena) + A_ur_bytes(*p) + 50 * A.np);
-  ra.fin_stride = 0;
+  RollArgs ra = arena_roll_args(make_arena(*p, arena));
   ra.trans = static_cast<char*>(trans);
   ra.trans_stride = trans_stride;
   ra.stage = static_cast<char*>(stage);
@@ -3072,7 +3159,6 @@ int sacenv_boat_segment(const SacenvBoatParams* p, void* arena, const float* act
   ra.ready = act_ready;
   ra.done = step_done;
   ra.seq0 = seq0;
-  ra.status = reinterpret_cast<int32_t*>(static_cast<char*>(arena) + status_offset(*p)) + 1;
   return launch_multi(*p, arena, actions, n_steps, ra, stream);
 }
 
@@ -3085,42 +3171,17 @@ int sacenv_boat_segment_occupancy(const SacenvBoatParams* p, int32_t with_trans,
   int rc = check_params(p);
   if (rc) return rc;
   if (blocks_per_cu == nullptr || grid == nullptr || vgprs == nullptr || lds_bytes == nullptr) return SACENV_E_NULL;
+  // the kernel launch_multi picks for a segment (strides 0) with these rows
+  const int nb_boat = (int)(pad64(p->n_envs) / kWave);
+  const int rows = with_trans == 2 ? 2 : with_trans ? 1 : 0;
+  const RolloutKernel k = rollout_kernel(*p, rows, lean_launch(*p, RollArgs{}), dense_grid(nb_boat));
   int nb = 0;
-  hipError_t e = hipSuccess;
   hipFuncAttributes fa{};
-  const bool dense = dense_grid((int)(pad64(p->n_envs) / kWave));  // the kernel launch_multi would pick
-  const bool lean = lean_launch(*p, RollArgs{});                   // (the segment's strides are 0)
-#define SACENV_OCC_ONE(K)                                                        \
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K, kWave, 0);            \
-  if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(K))
-#define SACENV_OCC_K(KER, NC, TI)                                                                            \
-  if (with_trans == 2 && lean) {                                                                             \
-    SACENV_OCC_ONE((KER<NC, TI, 2, true>));                                                                  \
-  } else if (with_trans == 0 && lean) {                                                                      \
-    SACENV_OCC_ONE((KER<NC, TI, 0, true>));                                                                  \
-  } else if (with_trans == 2) {                                                                              \
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KER<NC, TI, 2>, kWave, 0);                         \
-    if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(KER<NC, TI, 2>));       \
-  } else if (with_trans) {                                                                                   \
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KER<NC, TI, 1>, kWave, 0);                         \
-    if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(KER<NC, TI, 1>));       \
-  } else {                                                                                                   \
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KER<NC, TI, 0>, kWave, 0);                         \
-    if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(KER<NC, TI, 0>));       \
-  }
-#define SACENV_OCC(NC, TI)                  \
-  if (dense) {                              \
-    SACENV_OCC_K(k_rollout_dense, NC, TI);  \
-  } else {                                  \
-    SACENV_OCC_K(k_rollout, NC, TI);        \
-  }
-  SACENV_OWNER_DISPATCH(*p, SACENV_OCC)
-#undef SACENV_OCC
-#undef SACENV_OCC_K
-#undef SACENV_OCC_ONE
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kWave, 0);
+  if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k));
   if (e != hipSuccess) return (int)e;
   *blocks_per_cu = nb;
-  *grid = (int32_t)(pad64(p->n_envs) / kWave);
+  *grid = nb_boat;
   *vgprs = fa.numRegs;
   *lds_bytes = (int32_t)fa.sharedSizeBytes;
   return SACENV_OK;
@@ -3144,16 +3205,8 @@ int sacenv_boat_refill(const SacenvBoatParams* p, void* arena, void* stream) {
   // (+ the twist-ahead workgroups first, np / kAheadEnvs: measured ahead of
   // twisting in the fit blocks, before or after their fits)
   const int fit_blocks = 8192 + (int)(A.np / kAheadEnvs);
-  const Tail T = make_tail(*p, arena);
-  if (p->n_knots == 8)
-    hipLaunchKernelGGL((k_refill_fit<8, true>), dim3(fit_blocks), dim3(kWave), 0, (hipStream_t)stream, *p, A, T);
-  else if (p->n_knots < 8)
-    hipLaunchKernelGGL((k_refill_fit<8, false>), dim3(fit_blocks), dim3(kWave), 0, (hipStream_t)stream, *p, A, T);
-  else if (p->n_knots == 16)
-    hipLaunchKernelGGL((k_refill_fit<16, true>), dim3(fit_blocks), dim3(kWave), 0, (hipStream_t)stream, *p, A, T);
-  else
-    hipLaunchKernelGGL((k_refill_fit<16, false>), dim3(fit_blocks), dim3(kWave), 0, (hipStream_t)stream, *p, A,
-                       T);
+  hipLaunchKernelGGL(refill_fit_kernel(p->n_knots), dim3(fit_blocks), dim3(kWave), 0, (hipStream_t)stream, *p, A,
+                     make_tail(*p, arena));
   return launch_status();
 }
 
@@ -3198,38 +3251,12 @@ int sacenv_toy_step(const SacenvToyParams* p, void* arena, void* stream) {
 static int mixed_step(const SacenvBoatParams* bp, void* boat_arena, const float* boat_action,
                       const SacenvToyParams* toy_params, void* const* toy_arenas, int32_t n_toys,
                       char* trans, void* stream) {
-  int rc;
-  if (n_toys < 0 || n_toys > 2) return SACENV_E_SIZE;
-  if (n_toys > 0 && (toy_params == nullptr || toy_arenas == nullptr)) return SACENV_E_NULL;
-  MixedToys M{};
-  M.n = n_toys;
-  int nb = 0;
-  for (int t = 0; t < n_toys; ++t) {
-    if ((rc = check_toy(&toy_params[t]))) return rc;
-    if (toy_arenas[t] == nullptr) return SACENV_E_NULL;
-    M.p[t] = toy_params[t];
-    M.a[t] = make_toy_arena(toy_params[t], toy_arenas[t]);
-    M.nb[t] = blocks_for(toy_params[t].n_envs, kWave);
-    nb += M.nb[t];
-  }
-  SacenvBoatParams p{};
-  Arena A{};
-  Tail T{};
-  int nb_boat = 0;
-  if (bp != nullptr) {
-    if ((rc = check_params(bp))) return rc;
-    if (boat_arena == nullptr || boat_action == nullptr) return SACENV_E_NULL;
-    p = *bp;
-    A = make_arena(p, boat_arena);
-    T = make_tail(p, boat_arena);
-    nb_boat = (int)(pad64(p.n_envs) / kWave);
-    nb += nb_boat;
-  }
-  if (nb == 0) return SACENV_OK;
-#define SACENV_LAUNCH(NC, TI) \
-  hipLaunchKernelGGL((k_step<true, NC, TI>), dim3(nb), dim3(kWave), 0, (hipStream_t)stream, p, A, T, boat_action, nb_boat, M, trans)
-  SACENV_OWNER_DISPATCH(p, SACENV_LAUNCH)
-#undef SACENV_LAUNCH
+  MixedLaunch L;
+  const int rc = mixed_setup(bp, boat_arena, boat_action, toy_params, toy_arenas, n_toys, 1, &L);
+  if (rc) return rc;
+  if (L.nb == 0) return SACENV_OK;
+  hipLaunchKernelGGL(step_kernel(L.p, true), dim3(L.nb), dim3(kWave), 0, (hipStream_t)stream, L.p, L.A, L.T,
+                     boat_action, L.nb_boat, L.M, trans);
   return launch_status();
 }
 
@@ -3251,55 +3278,20 @@ int sacenv_mixed_step_pooled(const SacenvBoatParams* bp, void* boat_arena, const
 int sacenv_mixed_segment(const SacenvBoatParams* bp, void* boat_arena, const float* boat_actions,
                          int64_t action_stride, int32_t n_steps, const SacenvToyParams* toy_params,
                          void* const* toy_arenas, int32_t n_toys, void* stream) {
-  int rc;
-  if (n_toys < 0 || n_toys > 2) return SACENV_E_SIZE;
-  if (n_toys > 0 && (toy_params == nullptr || toy_arenas == nullptr)) return SACENV_E_NULL;
-  if (n_steps < 1) return SACENV_E_SIZE;
-  MixedToys M{};
-  M.n = n_toys;
-  int nb = 0;
-  for (int t = 0; t < n_toys; ++t) {
-    if ((rc = check_toy(&toy_params[t]))) return rc;
-    if (toy_arenas[t] == nullptr) return SACENV_E_NULL;
-    M.p[t] = toy_params[t];
-    M.a[t] = make_toy_arena(toy_params[t], toy_arenas[t]);
-    M.nb[t] = blocks_for(toy_params[t].n_envs, kWave);
-    nb += M.nb[t];
-  }
-  SacenvBoatParams p{};
-  Arena A{};
-  Tail T{};
+  MixedLaunch L;
+  const int rc = mixed_setup(bp, boat_arena, boat_actions, toy_params, toy_arenas, n_toys, n_steps, &L);
+  if (rc) return rc;
   RollArgs ra{};
-  int nb_boat = 0;
   if (bp != nullptr) {
-    if ((rc = check_params(bp))) return rc;
-    if (boat_arena == nullptr || boat_actions == nullptr) return SACENV_E_NULL;
     if (bp->autoreset && n_steps > SACENV_REFILL_PERIOD) return SACENV_E_SIZE;
     if (action_stride < bp->n_envs) return SACENV_E_RANGE;
-    p = *bp;
-    A = make_arena(p, boat_arena);
-    T = make_tail(p, boat_arena);
-    ra.rec = static_cast<char*>(boat_arena) + A_ur_bytes(p);
-    ra.rec_stride = 0;
-    ra.fin = reinterpret_cast<float*>(static_cast<char*>(boat_arena) + A_ur_bytes(p) + 50 * A.np);
-    ra.fin_stride = 0;
+    ra = arena_roll_args(L.A);
     ra.act_stride = action_stride;
-    ra.status = reinterpret_cast<int32_t*>(static_cast<char*>(boat_arena) + status_offset(p)) + 1;
-    nb_boat = (int)(pad64(p.n_envs) / kWave);
-    nb += nb_boat;
   }
-  if (nb == 0) return SACENV_OK;
+  if (L.nb == 0) return SACENV_OK;
   // (no boat: p is zeroed and no owner wave runs; the general instantiation)
-  const bool lean = lean_launch(p, ra);
-#define SACENV_LAUNCH(NC, TI)                                                                                  \
-  if (lean)                                                                                                    \
-    hipLaunchKernelGGL((k_rollout_mixed<NC, TI, true>), dim3(nb), dim3(kWave), 0, (hipStream_t)stream, p, A,   \
-                       T, boat_actions, n_steps, ra, nb_boat, M);                                              \
-  else                                                                                                         \
-    hipLaunchKernelGGL((k_rollout_mixed<NC, TI>), dim3(nb), dim3(kWave), 0, (hipStream_t)stream, p, A, T,      \
-                       boat_actions, n_steps, ra, nb_boat, M)
-  SACENV_OWNER_DISPATCH(p, SACENV_LAUNCH)
-#undef SACENV_LAUNCH
+  hipLaunchKernelGGL(rollout_mixed_kernel(L.p, lean_launch(L.p, ra)), dim3(L.nb), dim3(kWave), 0,
+                     (hipStream_t)stream, L.p, L.A, L.T, boat_actions, n_steps, ra, L.nb_boat, L.M);
   return launch_status();
 }
 

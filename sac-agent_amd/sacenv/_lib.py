@@ -26,6 +26,10 @@ STATUS_HANDOFF_TIMEOUT = 2
 STATUS_LIST_TIMEOUT = 4
 FLAG_ABORT = 0xFFFFFFFF  # hand-off flag of a wave / workgroup that gave up (sacenv.h)
 RECORD_BYTES = 50
+# the record's per-env byte columns (SACENV_REC_*): field f of n_pad envs starts at column * n_pad
+REC_OBS, REC_REWARD = 0, 4 * OBS_DIM
+REC_DONE, REC_TERM = RECORD_BYTES - 2, RECORD_BYTES - 1
+assert REC_REWARD + 4 == REC_DONE  # obs f32 x 11 | reward f32 | done u8 | term u8
 TRANS_OBS = 11          # s' entries in the pooled row (the whole obs)
 TRANS_BYTES = 53        # sacenv_boat_step_pooled's per-env transition row
 TRANS_BYTES_EXP2 = 57   # experiment 2 (+ obs3_next)

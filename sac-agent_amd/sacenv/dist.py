@@ -29,7 +29,7 @@ from dataclasses import dataclass
 
 import torch
 
-from ._lib import TRANS_OBS, trans_bytes  # noqa: F401
+from ._lib import OBS_DIM, REC_DONE, REC_OBS, REC_REWARD, REC_TERM, TRANS_OBS, trans_bytes  # noqa: F401
 from .vec_env import RECORD_BYTES
 
 
@@ -52,10 +52,11 @@ class RecordLayout:
         """(obs [n,11] f32, reward [n] f32, done [n] u8, term [n] u8) views of one record."""
         n = self.n
         if buf.dtype != torch.uint8 or buf.numel() != self.nbytes:
-            raise ValueError("record buffer must be uint8 of 50*n bytes")
-        obs = buf[: 44 * n].view(torch.float32).view(n, 11)
-        reward = buf[44 * n: 48 * n].view(torch.float32)
-        return obs, reward, buf[48 * n: 49 * n], buf[49 * n: 50 * n]
+            raise ValueError(f"record buffer must be uint8 of {RECORD_BYTES}*n bytes")
+        col = lambda a, b: buf[a * n: b * n]  # noqa: E731
+        obs = col(REC_OBS, REC_REWARD).view(torch.float32).view(n, OBS_DIM)
+        return (obs, col(REC_REWARD, REC_DONE).view(torch.float32), col(REC_DONE, REC_TERM),
+                col(REC_TERM, RECORD_BYTES))
 
     def pack(self, obs, reward, done, term) -> torch.Tensor:
         buf = torch.empty(self.nbytes, dtype=torch.uint8, device=obs.device)

@@ -370,9 +370,10 @@ class VecBoatEnv:
     def record_views(self, rec: torch.Tensor):
         """(obs [N, 11], reward [N], done [N], term [N]) views of one packed record."""
         NP, N = self.n_pad, self.num_envs
-        obs = rec[: 44 * NP].view(torch.float32).view(NP, _lib.OBS_DIM)[:N]
-        return (obs, rec[44 * NP: 48 * NP].view(torch.float32)[:N], rec[48 * NP: 49 * NP][:N],
-                rec[49 * NP: 50 * NP][:N])
+        col = lambda a, b: rec[a * NP: b * NP]  # noqa: E731
+        obs = col(_lib.REC_OBS, _lib.REC_REWARD).view(torch.float32).view(NP, _lib.OBS_DIM)[:N]
+        return (obs, col(_lib.REC_REWARD, _lib.REC_DONE).view(torch.float32)[:N],
+                col(_lib.REC_DONE, _lib.REC_TERM)[:N], col(_lib.REC_TERM, RECORD_BYTES)[:N])
 
     def _after_step(self) -> None:
         if self.autoreset:

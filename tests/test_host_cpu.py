@@ -240,11 +240,42 @@ def test_ctypes_structs_match_c_layout(tmp_path):
             assert got[(cname, fname)] == getattr(py, fname).offset, (cname, fname)
 
 
+# sacenv_boat_layout at ABI 20 before the record columns and the tail offsets were named
+# (commit 260a247), in LAYOUT_FIELDS order: the layout must not move
+LAYOUT_ABI20 = {
+    (1, False): (4780800, 64, 0, 8, 1024, 1032, 2048, 2056, 3072, 9216, 3080, 4096, 8192, 10752, 9728, 9984, 10240,
+                 10496, 11008, 76800, 78080, 79360, -1, 4290048, 4609536, 4609536, 4612352, 4612608, 4612672,
+                 4612736, 4615552, 4616064, 4617600, 4618240, 4618496, 4618752, 4620800, 79104, 4449792),
+    (63, True): (6886144, 64, 0, 8, 1024, 1032, 2048, 2056, 3072, 9216, 3080, 4096, 8192, 10752, 9728, 9984, 10240,
+                 10496, 11008, 76800, 78080, 79360, 4290048, 6395392, 6714880, 6714880, 6717696, 6717952, 6718016,
+                 6718080, 6720896, 6721408, 6722944, 6723584, 6723840, 6724096, 6726144, 79104, 6555136),
+    (64, False): (4780800, 64, 0, 8, 1024, 1032, 2048, 2056, 3072, 9216, 3080, 4096, 8192, 10752, 9728, 9984, 10240,
+                  10496, 11008, 76800, 78080, 79360, -1, 4290048, 4609536, 4609536, 4612352, 4612608, 4612672,
+                  4612736, 4615552, 4616064, 4617600, 4618240, 4618496, 4618752, 4620800, 79104, 4449792),
+    (65536, False): (4729117184, 65536, 0, 8, 1048576, 1048584, 2097152, 2097160, 3145728, 9437184, 3145736, 4194304,
+                     8388608, 11010048, 9961472, 10223616, 10485760, 10747904, 11272192, 78643200, 79953920,
+                     81264640, -1, 4393009152, 4720164864, 4720164864, 4723048448, 4723310592, 4723376128,
+                     4723441664, 4726325248, 4726849536, 4728422400, 4728946688, 4728954880, 4728955136,
+                     4728957184, 81002496, 4556587008),
+    (65536, True): (6884989440, 65536, 0, 8, 1048576, 1048584, 2097152, 2097160, 3145728, 9437184, 3145736, 4194304,
+                    8388608, 11010048, 9961472, 10223616, 10485760, 10747904, 11272192, 78643200, 79953920,
+                    81264640, 4393009152, 6548881408, 6876037120, 6876037120, 6878920704, 6879182848, 6879248384,
+                    6879313920, 6882197504, 6882721792, 6884294656, 6884818944, 6884827136, 6884827392,
+                    6884829440, 81002496, 6712459264),
+    (100000, False): (7218284032, 100032, 0, 8, 1600512, 1600520, 3201024, 3201032, 4801536, 14404608, 4801544,
+                      6402048, 12804096, 16805376, 15204864, 15604992, 16005120, 16405248, 17205504, 120038400,
+                      122039040, 124039680, -1, 6705345024, 7204704768, 7204704768, 7209106176, 7209506304,
+                      7209606336, 7209706368, 7214107776, 7214908032, 7217308800, 7218109184, 7218121728,
+                      7218121984, 7218124032, 123639552, 6955024896),
+}
+
+
 @pytest.mark.parametrize("n,knots", [(1, False), (63, True), (64, False), (65536, False), (65536, True),
                                      (100000, False)])
 def test_arena_layout(built_lib, n, knots):
     """Fields are aligned, disjoint and inside total_bytes; record is contiguous; the
-    drawn knots get storage only when recorded (SACENV_OUT_KNOTS)."""
+    drawn knots get storage only when recorded (SACENV_OUT_KNOTS); every field where
+    ABI 20 has had it; the record's columns as sacenv.h and _lib name them."""
     from sacenv import _lib
     from sacenv.config import BoatConfig, make_params
     p = make_params(BoatConfig(experiment=6), n, use_wind_table=True,
@@ -273,6 +304,12 @@ def test_arena_layout(built_lib, n, knots):
     for a0, a1, f in spans:
         assert a0 % 64 == 0, f
     assert L.record == L.obs and L.term + np_ == L.record + 50 * np_
+    assert len(LAYOUT_ABI20[(n, knots)]) == len(_lib.LAYOUT_FIELDS)
+    for f, want in zip(_lib.LAYOUT_FIELDS, LAYOUT_ABI20[(n, knots)]):
+        assert getattr(L, f) == want, f
+    assert (L.reward, L.done, L.term) == (L.obs + 44 * np_, L.obs + 48 * np_, L.obs + 49 * np_)
+    assert L.final_obs == L.record + 50 * np_
+    assert (_lib.REC_OBS, _lib.REC_REWARD, _lib.REC_DONE, _lib.REC_TERM, _lib.RECORD_BYTES) == (0, 44, 48, 49, 50)
     tail = [("refill_mask", 8 * np_ // 64), ("status", 256),
             ("spline_g", 8 * 256), ("wind_table", 16 * 10000)]
     end = spans[-1][1]

@@ -37,6 +37,21 @@ def kernel(text, name="k_rolloutILi2ELb1ELi0ELb1EE"):
     return lines[start:end]
 
 
+def split_kernels(text):
+    """{mangled name: lines} of every function in the file, each as kernel() returns it."""
+    out, cur = {}, None
+    for l in text.split("\n"):
+        if cur is None:
+            m = re.match(r"^(_Z\w+):", l)
+            if m:
+                cur = out[m.group(1)] = [l]
+        elif l.startswith(".Lfunc_end"):
+            cur = None
+        else:
+            cur.append(l)
+    return out
+
+
 def loops(lines):
     labels = {m.group(1): i for i, l in enumerate(lines) if (m := re.match(r"^(\.LBB\d+_\d+):", l))}
     out = []
