@@ -163,6 +163,20 @@ EXPORTS = ("sacenv_abi_version", "sacenv_error_string", "sacenv_boat_layout",
            "sacenv_compact_done", "sacenv_boat_reset_list", "sacenv_sac_layout", "sacenv_sac_sync",
            "sacenv_sac_act", "sacenv_sac_act_handoff", "sacenv_sac_act_occupancy", "sacenv_sac_learn")
 
+
+# include/sacenv_episodes.h (SACENV_EPISODES_VERSION 1): entry points beside the ABI of
+# sacenv.h, not counted in ABI_VERSION or EXPORTS; a library built before them still loads
+EPISODES_VERSION = 1
+EPISODE_ENTRY_BYTES = 32
+EPISODE_EXPORTS = ("sacenv_episodes_scratch_bytes", "sacenv_episodes_update")
+
+
+class EpisodeScan(C.Structure):
+    _fields_ = [("n_envs", _i32), ("n_pad", _i32), ("n_steps", _i32), ("env_base", _i32),
+                ("rec_stride", _i64), ("reward_off", _i64), ("done_off", _i64), ("term_off", _i64),
+                ("step0", _i64), ("cap", _i64)]
+
+
 _LIB = None
 
 
@@ -257,6 +271,11 @@ def load(path: str | None = None):
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
         f.restype, f.argtypes = res, args
+    ES = C.POINTER(EpisodeScan)
+    for name, args in zip(EPISODE_EXPORTS, ([ES, C.POINTER(_i64)], [ES, _p, _p, _p, _p, _i64, _p])):
+        f = getattr(lib, name, None)   # absent from a library built before sacenv_episodes.h
+        if f is not None:
+            f.restype, f.argtypes = C.c_int, args
     v = lib.sacenv_abi_version()
     if v != ABI_VERSION:
         raise SacenvError(f"libsacenv ABI {v} != expected {ABI_VERSION}")
