@@ -5,7 +5,9 @@ the torch restatement of ContinuousAgent that tests/test_agent_cpu.py pins to
 the reference agent itself (``sac_learn.npz``). Both are f32; only summation
 orders differ, so the tolerances are f32 ones:
 
-* choose_action: actions and log-probs within 2e-5 (absolute, values O(1));
+* choose_action: actions within 2e-5 (absolute, values O(1)); log-probs are not read
+  here (NativeSAC.choose_action passes no log_prob buffer): per row against a float64
+  oracle in tests/test_sac_native_f64_gpu.py, with per-element gradients and Adam;
 * gradients: with Adam's eps set to 1e3 an Adam step is -lr * g / 1e3 to
   within |g| / 1e3, i.e. linear in the gradient, so the parameter change of
   one learn() compares the gradients of all four losses: per tensor within
