@@ -1,0 +1,101 @@
+"""A hyper-parameter search on one GPU: P SAC agents, each on its own N boat envs.
+
+main.py -p (main.py:215-235) for P agents at once. The reference draws each agent's actor and
+critic learning rates, gamma and tau (utils/hyperparameter_tuner.py:20-43) and trains the agents
+as OS processes, three at a time; here they are the members of one ``NativeSACPopulation``:
+
+* one ``VecBoatEnv`` of P x N envs; member m owns envs [m N, (m + 1) N);
+* per step: one act launch for all members, one env step, one store per member into its own
+  ``DeviceReplayBuffer``, one learn (four launches) for all members;
+* an ``EpisodeLog`` on the env; an episode of env e belongs to member e // N.
+
+    python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
+
+Prints the members' drawn values (the four numbers a tuned_configs.yaml differs in, one line per
+member), then what main.py:99-114 prints per model -- Score (the last finished episode), Best
+Score, Average over the look-back -- and one JSON line with the same. ``--save DIR`` writes every
+member's checkpoints to DIR/member_<m>/checkpoints/.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "sac-agent_amd"))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--members", type=int, default=4)
+    ap.add_argument("--envs-per-member", type=int, default=1024)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--seed", type=int, default=0, help="seed of the hyper-parameter draws")
+    ap.add_argument("--lookback", type=int, default=100, help="avg_lookback (main.py:100-101)")
+    ap.add_argument("--save", default=None, help="directory for the members' checkpoints")
+    args = ap.parse_args(argv)
+    P, N = args.members, args.envs_per_member
+    if N < 64 or N % 64:
+        raise SystemExit("--envs-per-member must be a multiple of 64 (the act kernel's row block)")
+    from sacenv import NativeSACPopulation, VecBoatEnv, sample_hpsets
+    from sacenv.agent import AgentConfig
+    from sacenv.episodes import EpisodeLog
+    dev = torch.device("cuda")
+    configs = sample_hpsets(P, args.seed, base=AgentConfig(batch_size=args.batch))
+    pop = NativeSACPopulation(dev, configs, init_seeds=list(range(P)), buffer_seeds=list(range(P)))
+    for m, mem in enumerate(pop.members):
+        print(f"member {m}: " + json.dumps(mem.hpset()))
+    env = VecBoatEnv({"base_settings": {"experiment": 6, "test_mode": 0}}, P * N, seed=0, device=dev,
+                     max_episode_steps=500)
+    obs = env.reset().clone()
+    log = EpisodeLog(env)
+    # terminal as main.py:83-88 stores it: each env's last termination, kept per member
+    last_term = [torch.zeros(N, dtype=torch.uint8, device=dev) for _ in range(P)]
+    losses = None
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.iters):
+        a = pop.choose_action(obs.view(P, N, -1))
+        env.step(a.view(-1))
+        log.update()
+        for m in range(P):
+            rows = slice(m * N, (m + 1) * N)
+            pop.remember(m, obs[rows], a[m], env.reward[rows], env.obs[rows], env.term[rows],
+                         final_state=env.final_obs[rows], last_term=last_term[m])
+        obs = env.obs.clone()
+        out = pop.learn(losses=False)
+        losses = out if out is not None else losses
+    torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    entries = log.drain()
+    owner = entries["env"] // N
+    table = []
+    print(f"{'member':>6} {'episodes':>8} {'Score':>12} {'Best Score':>12} {'Average':>12}")
+    for m in range(P):
+        scores = entries["score"][owner == m]
+        row = {"member": m, "episodes": int(scores.size), **pop.members[m].hpset(),
+               "score": float(scores[-1]) if scores.size else None,
+               "best_score": float(scores.max()) if scores.size else None,
+               "avg_score": float(np.mean(scores[-args.lookback:])) if scores.size else None}
+        table.append(row)
+        fmt = lambda x: f"{x:12.2f}" if x is not None else f"{'-':>12}"  # noqa: E731
+        print(f"{m:>6} {row['episodes']:>8} {fmt(row['score'])} {fmt(row['best_score'])} {fmt(row['avg_score'])}")
+    if args.save:
+        pop.save_models(args.save, optimizer=True)
+    out = {"pipeline": "population act + VecBoatEnv.step + per-member store + per-member sample + population learn",
+           "members": P, "envs_per_member": N, "iters": args.iters, "batch": args.batch,
+           "env_steps_per_s": P * N * args.iters / el, "ms_per_iter": el / args.iters * 1e3,
+           "losses": None if losses is None else losses.tolist(), "table": table}
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()

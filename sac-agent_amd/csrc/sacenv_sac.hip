@@ -39,6 +39,7 @@
 #include <math.h>
 
 #include "sacenv.h"
+#include "sacenv_population.h"
 
 namespace {
 
@@ -654,6 +655,7 @@ __device__ __forceinline__ void rows_body(const SacArgs& a, RowLds& l, int phase
   }
 }
 
+#ifndef SACENV_SAC_BODIES_ONLY  // sacenv_sac_pop.hip includes this file for the device bodies and host helpers alone
 // one or two workgroups per CU: registers for kPrefetch k-blocks of weights in flight
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 2))) k_sac_rows(SacArgs a, int phase) {
   __shared__ RowLds l;
@@ -661,6 +663,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
   rows_body(a, l, phase, blockIdx.x);
   STAMP(a, phase, 15);
 }
+#endif  // SACENV_SAC_BODIES_ONLY
 
 // ---------------------------------------------------------------- phase 3: gradients + Adam
 
@@ -906,6 +909,7 @@ __device__ __forceinline__ void update_body(const SacArgs& a, float* sm, int b) 
 }
 constexpr int kUpdateBlocks = 1 + kSmallBlocks + 4 * kFc2Tiles;
 
+#ifndef SACENV_SAC_BODIES_ONLY  // sacenv_sac_pop.hip includes this file for the device bodies and host helpers alone
 __global__ void __launch_bounds__(kThreads) k_sac_update(SacArgs a) {
   __shared__ float sm[kUpdLds];
   STAMP(a, 3, 0);
@@ -924,6 +928,7 @@ __global__ void __launch_bounds__(kThreads) k_sac_sync(SacArgs a) {
     if (t < 4) a.P[a.w2tf[t] + swz(k, n)] = v;
   }
 }
+#endif  // SACENV_SAC_BODIES_ONLY
 
 // choose_action for n rows: actor forward and the sample() draw. 64 rows per
 // workgroup (four 16-row tiles against every weight fragment: 4x the MFMA
@@ -1174,8 +1179,63 @@ SacArgs make_args(const SacenvSacParams* p, float* weights) {
 
 bool aligned16(const void* q) { return ((uintptr_t)q & 15u) == 0; }
 
+// What one agent's learn() has of its own, as the f32 values the kernels read:
+// the casts of the reference's Python floats, and Adam's step sizes as
+// torch.optim.Adam (_multi_tensor_adam) forms them, (lr / bias_correction1) * -1.
+// sacenv_sac_learn and sacenv_sac_pop_learn both take them from here.
+struct PopMember {
+  float gamma, scale, tau, omtau, nstep_actor, nstep_critic;
+};
+
+PopMember member_scalars(double lr_actor, double lr_critic, double gamma, double tau, double reward_scale,
+                         double bc1) {
+  PopMember m;
+  m.gamma = (float)gamma;
+  m.scale = (float)reward_scale;
+  m.tau = (float)tau;
+  m.omtau = (float)(1.0 - tau);
+  m.nstep_actor = (float)((lr_actor / bc1) * -1.0);
+  m.nstep_critic = (float)((lr_critic / bc1) * -1.0);
+  return m;
+}
+
+void set_member(SacArgs& a, const PopMember& m) {
+  a.gamma = m.gamma;
+  a.scale = m.scale;
+  a.tau = m.tau;
+  a.omtau = m.omtau;
+  a.nstep_actor = m.nstep_actor;
+  a.nstep_critic = m.nstep_critic;
+}
+
+// The learn() arguments every agent of a call shares: the scratch partition and
+// Adam's scalars (torch.optim.Adam: Python-float scalars, cast to f32 in the
+// kernels). Returns bias_correction1 = 1 - beta1^step.
+double set_learn_common(SacArgs& a, const SacenvSacParams* p, void* scratch, int32_t adam_step) {
+  float* scr = static_cast<float*>(scratch);
+  const int64_t tile = (int64_t)kH * p->batch;
+  for (int t = 0; t < 4; ++t) {
+    a.na[t].h1t = scr + (4 * t + 0) * tile;
+    a.na[t].h2t = scr + (4 * t + 1) * tile;
+    a.na[t].dz1t = scr + (4 * t + 2) * tile;
+    a.na[t].dz2t = scr + (4 * t + 3) * tile;
+  }
+  a.rows = scr + 16 * tile;
+  a.xt = a.rows + (int64_t)F_COUNT * p->batch;
+  a.stamps = reinterpret_cast<unsigned long long*>(a.xt + 16 * (int64_t)p->batch);
+  const double b1 = p->adam_beta1, b2 = p->adam_beta2;
+  const double bc1 = 1.0 - pow(b1, (double)adam_step), bc2 = 1.0 - pow(b2, (double)adam_step);
+  a.lerp_w = (float)(1.0 - b1);
+  a.b2 = (float)b2;
+  a.omb2 = (float)(1.0 - b2);
+  a.bc2s = (float)pow(bc2, 0.5);
+  a.eps = (float)p->adam_eps;
+  return bc1;
+}
+
 }  // namespace
 
+#ifndef SACENV_SAC_BODIES_ONLY  // sacenv_sac_pop.hip includes this file for the device bodies and host helpers alone
 extern "C" int sacenv_sac_layout(const SacenvSacParams* p, SacenvSacLayout* out) {
   if (p == nullptr || out == nullptr) return SACENV_E_NULL;
   const int rc = check(p);
@@ -1292,27 +1352,8 @@ extern "C" int sacenv_sac_learn(const SacenvSacParams* p, float* weights, void* 
   a.eps1 = eps1;
   a.eps2 = eps2;
   a.losses = losses;
-  float* scr = static_cast<float*>(scratch);
-  const int64_t tile = (int64_t)kH * p->batch;
-  for (int t = 0; t < 4; ++t) {
-    a.na[t].h1t = scr + (4 * t + 0) * tile;
-    a.na[t].h2t = scr + (4 * t + 1) * tile;
-    a.na[t].dz1t = scr + (4 * t + 2) * tile;
-    a.na[t].dz2t = scr + (4 * t + 3) * tile;
-  }
-  a.rows = scr + 16 * tile;
-  a.xt = a.rows + (int64_t)F_COUNT * p->batch;
-  a.stamps = reinterpret_cast<unsigned long long*>(a.xt + 16 * (int64_t)p->batch);
-  // torch.optim.Adam (_multi_tensor_adam): Python-float scalars, cast to f32 in the kernels
-  const double b1 = p->adam_beta1, b2 = p->adam_beta2;
-  const double bc1 = 1.0 - pow(b1, (double)adam_step), bc2 = 1.0 - pow(b2, (double)adam_step);
-  a.lerp_w = (float)(1.0 - b1);
-  a.b2 = (float)b2;
-  a.omb2 = (float)(1.0 - b2);
-  a.bc2s = (float)pow(bc2, 0.5);
-  a.eps = (float)p->adam_eps;
-  a.nstep_actor = (float)((p->lr_actor / bc1) * -1.0);
-  a.nstep_critic = (float)((p->lr_critic / bc1) * -1.0);
+  const double bc1 = set_learn_common(a, p, scratch, adam_step);
+  set_member(a, member_scalars(p->lr_actor, p->lr_critic, p->gamma, p->tau, p->reward_scale, bc1));
   const int nrb = p->batch / kRows;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_sac_rows, dim3(4 * nrb), dim3(kThreads), 0, s, a, 0);
@@ -1321,3 +1362,4 @@ extern "C" int sacenv_sac_learn(const SacenvSacParams* p, float* weights, void* 
   hipLaunchKernelGGL(k_sac_update, dim3(kUpdateBlocks), dim3(kThreads), 0, s, a);
   return (int)hipGetLastError();
 }
+#endif  // SACENV_SAC_BODIES_ONLY

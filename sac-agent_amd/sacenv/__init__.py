@@ -9,7 +9,7 @@ from .config import BoatConfig
 from .spaces import Box
 
 __all__ = ["BoatConfig", "Box", "VecBoatEnv", "BoatEnv", "ParachuteEnv", "CarEnv", "VecToyEnv",
-           "MixedBatch", "_lib"]
+           "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "_lib"]
 
 
 def __getattr__(name):  # lazy: importing torch-dependent classes only when used
@@ -22,4 +22,7 @@ def __getattr__(name):  # lazy: importing torch-dependent classes only when used
     if name in ("ParachuteEnv", "CarEnv", "VecToyEnv", "MixedBatch"):
         from . import toys
         return getattr(toys, name)
+    if name in ("NativeSACPopulation", "sample_hpsets", "HPRanges"):
+        from . import population
+        return getattr(population, name)
     raise AttributeError(name)

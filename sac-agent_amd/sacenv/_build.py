@@ -16,7 +16,8 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 BUILD = os.path.join(PKG_ROOT, "build")
 LIB = os.path.join(BUILD, "libsacenv.so")
-SOURCES = ("sacenv_boat.hip", "sacenv_replay.hip", "sacenv_sac.hip", "sacenv_episodes.hip")
+SOURCES = ("sacenv_boat.hip", "sacenv_replay.hip", "sacenv_sac.hip", "sacenv_episodes.hip",
+           "sacenv_sac_pop.hip")   # (includes sacenv_sac.hip for its device bodies)
 HEADERS = ("mt19937.h",)
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fPIC", "-shared", "-Wall")
@@ -25,7 +26,7 @@ HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 def deps() -> list[tuple[str, str]]:
     """(path relative to the repo root, absolute path) of every input file."""
     rel = [os.path.join("sac-agent_amd", "csrc", f) for f in SOURCES + HEADERS]
-    rel += [os.path.join("include", h) for h in ("sacenv.h", "sacenv_episodes.h")]
+    rel += [os.path.join("include", h) for h in ("sacenv.h", "sacenv_episodes.h", "sacenv_population.h")]
     return [(r, os.path.join(REPO_ROOT, r)) for r in rel]
 
 

@@ -177,6 +177,23 @@ class EpisodeScan(C.Structure):
                 ("step0", _i64), ("cap", _i64)]
 
 
+# include/sacenv_population.h (SACENV_POPULATION_VERSION 1): P SAC agents in one set of
+# launches; beside the ABI of sacenv.h as the episode log is, bound only where the library has them
+POPULATION_VERSION = 1
+POPULATION_MAX_MEMBERS = 64
+POPULATION_EXPORTS = ("sacenv_sac_pop_layout", "sacenv_sac_pop_sync", "sacenv_sac_pop_act",
+                      "sacenv_sac_pop_learn")
+
+
+class SacMember(C.Structure):
+    _fields_ = [("lr_actor", _d), ("lr_critic", _d), ("gamma", _d), ("tau", _d), ("reward_scale", _d)]
+
+
+class SacPopLayout(C.Structure):
+    _fields_ = [("member_floats", _i64), ("scratch_bytes", _i64), ("total_floats", _i64),
+                ("total_scratch_bytes", _i64), ("max_members", _i32), ("pad", _i32)]
+
+
 _LIB = None
 
 
@@ -276,6 +293,14 @@ def load(path: str | None = None):
         f = getattr(lib, name, None)   # absent from a library built before sacenv_episodes.h
         if f is not None:
             f.restype, f.argtypes = C.c_int, args
+    QP = C.POINTER(SacParams)
+    for name, args in zip(POPULATION_EXPORTS, (
+            [QP, _i32, C.POINTER(SacPopLayout)], [QP, _i32, _p, _p],
+            [QP, _i32, _p, _p, _i32, _p, _p, _p, _p],
+            [QP, _i32, C.POINTER(SacMember), _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p])):
+        f = getattr(lib, name, None)   # absent from a library built before sacenv_population.h
+        if f is not None:
+            f.restype, f.argtypes = C.c_int, args
     v = lib.sacenv_abi_version()
     if v != ABI_VERSION:
         raise SacenvError(f"libsacenv ABI {v} != expected {ABI_VERSION}")
@@ -308,6 +333,12 @@ def toy_layout(params: ToyParams) -> ToyLayout:
 def sac_layout(params: SacParams) -> SacLayout:
     out = SacLayout()
     check(load().sacenv_sac_layout(C.byref(params), C.byref(out)))
+    return out
+
+
+def sac_pop_layout(params: SacParams, members: int) -> SacPopLayout:
+    out = SacPopLayout()
+    check(load().sacenv_sac_pop_layout(C.byref(params), int(members), C.byref(out)))
     return out
 
 
