@@ -5,11 +5,15 @@ critic learning rates, gamma and tau (utils/hyperparameter_tuner.py:20-43) and t
 as OS processes, three at a time; here they are the members of one ``NativeSACPopulation``:
 
 * one ``VecBoatEnv`` of P x N envs; member m owns envs [m N, (m + 1) N);
-* per step: one act launch for all members, one env step, one store per member into its own
-  ``DeviceReplayBuffer``, one learn (four launches) for all members;
+* per step: one act launch for all members, one env step, one store launch and one sample (two
+  launches) for all members through a ``PopulationReplay``, one learn (four launches) for all
+  members; ``--replay members`` keeps one ``DeviceReplayBuffer`` per member instead (a store, a
+  draw and a gather launch per member and five stack copies per step): the same table and
+  losses, bit for bit;
 * an ``EpisodeLog`` on the env; an episode of env e belongs to member e // N.
 
     python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
+        [--replay population|members]
 
 Prints the members' drawn values (the four numbers a tuned_configs.yaml differs in, one line per
 member), then what main.py:99-114 prints per model -- Score (the last finished episode), Best
@@ -40,16 +44,22 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="seed of the hyper-parameter draws")
     ap.add_argument("--lookback", type=int, default=100, help="avg_lookback (main.py:100-101)")
     ap.add_argument("--save", default=None, help="directory for the members' checkpoints")
+    ap.add_argument("--replay", choices=("population", "members"), default="population",
+                    help="one PopulationReplay for all members, or one DeviceReplayBuffer per member")
     args = ap.parse_args(argv)
     P, N = args.members, args.envs_per_member
     if N < 64 or N % 64:
         raise SystemExit("--envs-per-member must be a multiple of 64 (the act kernel's row block)")
-    from sacenv import NativeSACPopulation, VecBoatEnv, sample_hpsets
+    from sacenv import NativeSACPopulation, PopulationReplay, VecBoatEnv, sample_hpsets
     from sacenv.agent import AgentConfig
     from sacenv.episodes import EpisodeLog
     dev = torch.device("cuda")
     configs = sample_hpsets(P, args.seed, base=AgentConfig(batch_size=args.batch))
-    pop = NativeSACPopulation(dev, configs, init_seeds=list(range(P)), buffer_seeds=list(range(P)))
+    pooled = args.replay == "population"
+    replay = None
+    if pooled:  # the members' buffers in one arena, with the seeds the per-member buffers get
+        replay = PopulationReplay(P, configs[0].max_size, (11,), 1, device=dev, seeds=list(range(P)))
+    pop = NativeSACPopulation(dev, configs, init_seeds=list(range(P)), buffer_seeds=list(range(P)), replay=replay)
     for m, mem in enumerate(pop.members):
         print(f"member {m}: " + json.dumps(mem.hpset()))
     env = VecBoatEnv({"base_settings": {"experiment": 6, "test_mode": 0}}, P * N, seed=0, device=dev,
@@ -65,7 +75,9 @@ def main(argv=None):
         a = pop.choose_action(obs.view(P, N, -1))
         env.step(a.view(-1))
         log.update()
-        for m in range(P):
+        if pooled:  # member m's rows are envs [m N, (m + 1) N): the env's outputs as they lie
+            replay.store_env_step(obs, a, env)
+        for m in range(0 if pooled else P):
             rows = slice(m * N, (m + 1) * N)
             pop.remember(m, obs[rows], a[m], env.reward[rows], env.obs[rows], env.term[rows],
                          final_state=env.final_obs[rows], last_term=last_term[m])
@@ -89,7 +101,9 @@ def main(argv=None):
         print(f"{m:>6} {row['episodes']:>8} {fmt(row['score'])} {fmt(row['best_score'])} {fmt(row['avg_score'])}")
     if args.save:
         pop.save_models(args.save, optimizer=True)
-    out = {"pipeline": "population act + VecBoatEnv.step + per-member store + per-member sample + population learn",
+    out = {"pipeline": "population act + VecBoatEnv.step + " + ("population store + population sample" if pooled else
+                                                                  "per-member store + per-member sample")
+                       + " + population learn", "replay": args.replay,
            "members": P, "envs_per_member": N, "iters": args.iters, "batch": args.batch,
            "env_steps_per_s": P * N * args.iters / el, "ms_per_iter": el / args.iters * 1e3,
            "losses": None if losses is None else losses.tolist(), "table": table}

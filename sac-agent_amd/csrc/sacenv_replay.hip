@@ -65,7 +65,11 @@ struct RB {
   __device__ int32_t* pos() const { return reinterpret_cast<int32_t*>(b + L.mt_pos); }
 };
 
-__global__ void __launch_bounds__(kWave) k_rb_init(RB r, uint32_t seed) {
+// The bodies of the five one-buffer kernels are device functions: sacenv_replay_pop.hip
+// includes this file with SACENV_REPLAY_BODIES_ONLY (the kernels and entry points compiled
+// out) and runs them under a second grid dimension over the members of a population. They
+// index by blockIdx.x / gridDim.x only.
+__device__ __forceinline__ void init_body(const RB& r, uint32_t seed) {
   if (threadIdx.x != 0) return;
   uint32_t x = seed;  // init_genrand (numpy RandomState._legacy_seeding)
   for (int i = 0; i < kMtN; ++i) {
@@ -75,6 +79,10 @@ __global__ void __launch_bounds__(kWave) k_rb_init(RB r, uint32_t seed) {
   *r.pos() = kMtN;
   *r.cntr() = 0;
 }
+
+#ifndef SACENV_REPLAY_BODIES_ONLY  // sacenv_replay_pop.hip includes this file for the device bodies and host helpers alone
+__global__ void __launch_bounds__(kWave) k_rb_init(RB r, uint32_t seed) { init_body(r, seed); }
+#endif  // SACENV_REPLAY_BODIES_ONLY
 
 // store_transition for rows [0, n): row i -> (mem_cntr + i) % M. Rows that a
 // later row of the same call overwrites (i < n - M) are skipped, so the ring
@@ -86,15 +94,12 @@ __global__ void __launch_bounds__(kWave) k_rb_init(RB r, uint32_t seed) {
 // count from the host (host_cntr >= 0) no workgroup reads it, so the first one
 // writes the advanced count and the second launch goes (one fixed launch cost,
 // ~5 us, per stored step).
-__global__ void __launch_bounds__(256) k_rb_store(SacenvReplayParams p, RB r, int64_t host_cntr, int64_t advance,
-                                                  int64_t n, int64_t offset,
-                                                  const float* __restrict__ state,
-                                                  const float* __restrict__ action,
-                                                  const void* __restrict__ reward,
-                                                  const float* __restrict__ new_state,
-                                                  const float* __restrict__ final_state,
-                                                  const uint8_t* __restrict__ code,
-                                                  uint8_t* __restrict__ last_term) {
+__device__ __forceinline__ void store_body(const SacenvReplayParams& p, const RB& r, int64_t host_cntr,
+                                           int64_t advance, int64_t n, int64_t offset,
+                                           const float* __restrict__ state, const float* __restrict__ action,
+                                           const void* __restrict__ reward, const float* __restrict__ new_state,
+                                           const float* __restrict__ final_state, const uint8_t* __restrict__ code,
+                                           uint8_t* __restrict__ last_term) {
   const int64_t M = p.mem_size, c0 = (host_cntr >= 0 ? host_cntr : *r.cntr()) + offset;
   if (host_cntr >= 0 && blockIdx.x == 0 && threadIdx.x == 0) *r.cntr() = host_cntr + advance;  // buffer.py:22
   const int64_t first = n > M ? n - M : 0;
@@ -142,9 +147,25 @@ __global__ void __launch_bounds__(256) k_rb_store(SacenvReplayParams p, RB r, in
   }
 }
 
-__global__ void k_rb_advance(RB r, int64_t n) {
+__device__ __forceinline__ void advance_body(const RB& r, int64_t n) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *r.cntr() += n;  // buffer.py:22
 }
+
+#ifndef SACENV_REPLAY_BODIES_ONLY
+__global__ void __launch_bounds__(256) k_rb_store(SacenvReplayParams p, RB r, int64_t host_cntr, int64_t advance,
+                                                  int64_t n, int64_t offset,
+                                                  const float* __restrict__ state,
+                                                  const float* __restrict__ action,
+                                                  const void* __restrict__ reward,
+                                                  const float* __restrict__ new_state,
+                                                  const float* __restrict__ final_state,
+                                                  const uint8_t* __restrict__ code,
+                                                  uint8_t* __restrict__ last_term) {
+  store_body(p, r, host_cntr, advance, n, offset, state, action, reward, new_state, final_state, code, last_term);
+}
+
+__global__ void k_rb_advance(RB r, int64_t n) { advance_body(r, n); }
+#endif  // SACENV_REPLAY_BODIES_ONLY
 
 // np.random.choice(max_mem, batch) with replace=True, p=None: numpy legacy
 // randint(0, max_mem) -> masked rejection on 32-bit words (rng = max_mem-1;
@@ -166,10 +187,10 @@ __device__ __forceinline__ bool owns(const Shard& sh, int64_t cnt, int64_t M, in
   return u >= sh.lo && u < sh.hi;
 }
 
-__global__ void __launch_bounds__(256) k_rb_gather(SacenvReplayParams p, RB r, int batch,
-                                                   const int64_t* __restrict__ idx, float* __restrict__ st,
-                                                   float* __restrict__ ac, double* __restrict__ rw,
-                                                   float* __restrict__ ns, uint8_t* __restrict__ tm, Shard sh) {
+__device__ __forceinline__ void gather_body(const SacenvReplayParams& p, const RB& r, int batch,
+                                            const int64_t* __restrict__ idx, float* __restrict__ st,
+                                            float* __restrict__ ac, double* __restrict__ rw,
+                                            float* __restrict__ ns, uint8_t* __restrict__ tm, const Shard& sh) {
   const int D = p.obs_dim, A = p.act_dim;
   const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t nd = (int64_t)batch * D, na = (int64_t)batch * A;
@@ -190,6 +211,15 @@ __global__ void __launch_bounds__(256) k_rb_gather(SacenvReplayParams p, RB r, i
     if (tm) tm[i] = own ? r.terminal()[row] : (uint8_t)0;
   }
 }
+
+#ifndef SACENV_REPLAY_BODIES_ONLY
+__global__ void __launch_bounds__(256) k_rb_gather(SacenvReplayParams p, RB r, int batch,
+                                                   const int64_t* __restrict__ idx, float* __restrict__ st,
+                                                   float* __restrict__ ac, double* __restrict__ rw,
+                                                   float* __restrict__ ns, uint8_t* __restrict__ tm, Shard sh) {
+  gather_body(p, r, batch, idx, st, ac, rw, ns, tm, sh);
+}
+#endif  // SACENV_REPLAY_BODIES_ONLY
 
 // ---------------------------------------------------------------------------
 // The staged sampler: the pooled buffer of main.py:78-90 -- every rank's envs
@@ -265,10 +295,9 @@ __device__ __forceinline__ void mt_twist_block(const uint32_t* __restrict__ o, u
 // kSample: one sample_buffer(batch) at the device count (sacenv_replay_sample: no
 // learn() skip below batch rows; graph-capturable like the store), else the nb
 // learns of a staged segment at counts cntr0 + (k + 1) * period.
-template <bool kSample = false>
-__global__ void __launch_bounds__(kDrawThreads) k_rb_draw_many(SacenvReplayParams p, RB r, int batch, int nb,
-                                                               int64_t cntr0, int64_t period,
-                                                               int64_t* __restrict__ idx) {
+template <bool kSample>
+__device__ __forceinline__ void draw_many_body(const SacenvReplayParams& p, const RB& r, int batch, int nb,
+                                               int64_t cntr0, int64_t period, int64_t* __restrict__ idx) {
   __shared__ uint32_t blk[2][kMtN];
   __shared__ int wcnt[kDrawThreads / kWave];
   __shared__ int s_end;
@@ -336,6 +365,14 @@ __global__ void __launch_bounds__(kDrawThreads) k_rb_draw_many(SacenvReplayParam
   if (advanced)
     for (int i = tid; i < kMtN; i += kDrawThreads) r.key()[i] = blk[cur][i];
   if (tid == 0) *r.pos() = pos;
+}
+
+#ifndef SACENV_REPLAY_BODIES_ONLY  // (down to the host helpers: the staged, side and stand-in kernels)
+template <bool kSample = false>
+__global__ void __launch_bounds__(kDrawThreads) k_rb_draw_many(SacenvReplayParams p, RB r, int batch, int nb,
+                                                               int64_t cntr0, int64_t period,
+                                                               int64_t* __restrict__ idx) {
+  draw_many_body<kSample>(p, r, batch, nb, cntr0, period, idx);
 }
 
 // The steady-state path (every learn of the segment draws from the same range
@@ -1050,6 +1087,7 @@ __global__ void __launch_bounds__(256) k_copy_standin(const uint4* __restrict__ 
 
 // 32-bit words of one learn's batch in sacenv_replay_sample_staged's packing
 int64_t words_per_batch(int32_t batch) { return (int64_t)batch * (2 * SACENV_OBS_DIM + 1 + 3); }
+#endif  // SACENV_REPLAY_BODIES_ONLY
 
 int check_replay(const SacenvReplayParams* p) {
   if (p == nullptr) return SACENV_E_NULL;
@@ -1072,6 +1110,7 @@ int status() {
 
 }  // namespace
 
+#ifndef SACENV_REPLAY_BODIES_ONLY  // sacenv_replay_pop.hip includes this file for the device bodies and host helpers alone
 extern "C" {
 
 int sacenv_replay_layout(const SacenvReplayParams* p, SacenvReplayLayout* out) {
@@ -1557,3 +1596,4 @@ int sacenv_copy_standin(const void* src, void* dst, int64_t bytes, int32_t workg
 }
 
 }  // extern "C"
+#endif  // SACENV_REPLAY_BODIES_ONLY

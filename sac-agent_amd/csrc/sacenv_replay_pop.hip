@@ -1,0 +1,200 @@
+// sacenv_replay_pop.hip — the replay buffers of a population in one set of launches
+// (include/sacenv_population_replay.h; the buffers of the reference's hyper-parameter
+// search, main.py -p N: one agent/buffer.py ring and one np.random stream per agent).
+//
+// P buffers: the one-buffer kernels of sacenv_replay.hip with a second grid dimension
+// over the members. Member m = blockIdx.y runs init_body / store_body / advance_body /
+// draw_many_body<true> / gather_body, unchanged, on its own RB -- the launch's RB
+// (member 0's base and the layout all members share) with the base moved by m x
+// member_bytes -- and on its own rows of the [P][n][..] inputs and [P][batch][..]
+// outputs. The bodies index by blockIdx.x / gridDim.x only. No per-member struct is
+// indexed by a run-time value (that costs scratch); the one
+// per-member table, the seeds of the init launch, is read from the kernel arguments
+// with scalar loads at an SGPR offset, as PopArgs is in sacenv_sac_pop.hip.
+//
+// This is a translation unit of its own, which includes sacenv_replay.hip for the
+// device bodies and the host helpers: the one-buffer kernels, and above all the
+// staged, side and stand-in kernels of the timed replay path, are compiled where
+// they were, alone (tools/kernel_diff.py; DESIGN.md §4.6.1 has the result and the
+// resource table).
+#define SACENV_REPLAY_BODIES_ONLY
+#include "sacenv_replay.hip"
+
+#include "sacenv_population_replay.h"
+
+namespace {
+
+constexpr int kRbPopMax = SACENV_REPLAY_POP_MAX_MEMBERS;
+
+struct PopSeeds {
+  uint32_t v[kRbPopMax];
+};
+
+__device__ __forceinline__ RB member_rb(const RB& r, int64_t member_bytes, int64_t m) {
+  RB rm = r;
+  rm.b = r.b + m * member_bytes;
+  return rm;
+}
+
+// grid (1, P)
+__global__ void __launch_bounds__(kWave) k_rb_init_pop(RB r, int64_t member_bytes, PopSeeds seeds) {
+  init_body(member_rb(r, member_bytes, blockIdx.y), seeds.v[blockIdx.y]);
+}
+
+// grid (min(blocks, 8192), P): member m's n rows of the [P][n][..] inputs
+__global__ void __launch_bounds__(256) k_rb_store_pop(SacenvReplayParams p, RB r, int64_t member_bytes,
+                                                      int64_t host_cntr, int64_t advance, int64_t n,
+                                                      const float* __restrict__ state,
+                                                      const float* __restrict__ action,
+                                                      const void* __restrict__ reward,
+                                                      const float* __restrict__ new_state,
+                                                      const float* __restrict__ final_state,
+                                                      const uint8_t* __restrict__ code,
+                                                      uint8_t* __restrict__ last_term) {
+  const int64_t m = blockIdx.y, rows = m * n, D = p.obs_dim, A = p.act_dim;
+  store_body(p, member_rb(r, member_bytes, m), host_cntr, advance, n, 0, state + rows * D, action + rows * A,
+             static_cast<const char*>(reward) + rows * (p.reward_f32 ? 4 : 8), new_state + rows * D,
+             final_state != nullptr ? final_state + rows * D : nullptr, code + rows,
+             last_term != nullptr ? last_term + rows : nullptr);
+}
+
+// grid (1, P)
+__global__ void k_rb_advance_pop(RB r, int64_t member_bytes, int64_t n) {
+  advance_body(member_rb(r, member_bytes, blockIdx.y), n);
+}
+
+// grid (1, P) x 1 024 threads: one workgroup per member, each on its own key, position and count
+__global__ void __launch_bounds__(kDrawThreads) k_rb_draw_pop(SacenvReplayParams p, RB r, int64_t member_bytes,
+                                                              int batch, int64_t* __restrict__ idx) {
+  const int64_t m = blockIdx.y;
+  draw_many_body<true>(p, member_rb(r, member_bytes, m), batch, 1, 0, 0, idx + m * batch);
+}
+
+// grid (ceil(batch x (D + A + 1) / 256), P): member m's rows into the [P][batch][..] outputs
+__global__ void __launch_bounds__(256) k_rb_gather_pop(SacenvReplayParams p, RB r, int64_t member_bytes, int batch,
+                                                       const int64_t* __restrict__ idx, float* __restrict__ st,
+                                                       float* __restrict__ ac, double* __restrict__ rw,
+                                                       float* __restrict__ ns, uint8_t* __restrict__ tm) {
+  const int64_t m = blockIdx.y, rows = m * batch, D = p.obs_dim, A = p.act_dim;
+  gather_body(p, member_rb(r, member_bytes, m), batch, idx + rows, st != nullptr ? st + rows * D : nullptr,
+              ac != nullptr ? ac + rows * A : nullptr, rw != nullptr ? rw + rows : nullptr,
+              ns != nullptr ? ns + rows * D : nullptr, tm != nullptr ? tm + rows : nullptr, Shard{0, 0, 0});
+}
+
+int rb_pop_check(const SacenvReplayParams* p, int32_t members) {
+  const int rc = check_replay(p);
+  if (rc) return rc;
+  if (members < 1 || members > kRbPopMax) return SACENV_E_SIZE;
+  return SACENV_OK;
+}
+
+bool aligned256(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 255u) == 0u; }
+
+int gather_pop(const SacenvReplayParams* p, int32_t members, const RB& r, int32_t batch, const int64_t* idx,
+               float* state, float* action, double* reward, float* new_state, uint8_t* terminal, void* stream) {
+  const int64_t total = (int64_t)batch * (p->obs_dim + p->act_dim + 1);
+  hipLaunchKernelGGL(k_rb_gather_pop, dim3((unsigned)((total + 255) / 256), members), dim3(256), 0,
+                     (hipStream_t)stream, *p, r, r.L.total_bytes, batch, idx, state, action, reward, new_state,
+                     terminal);
+  return status();
+}
+
+// a member's elements of one sample or gather: the gather's grid.x is their count / 256
+bool batch_fits(const SacenvReplayParams* p, int32_t batch) {
+  return (int64_t)batch * ((int64_t)p->obs_dim + p->act_dim + 1) < (1LL << 32);
+}
+
+}  // namespace
+
+extern "C" int sacenv_replay_pop_layout(const SacenvReplayParams* p, int32_t members, SacenvReplayPopLayout* out) {
+  const int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (out == nullptr) return SACENV_E_NULL;
+  SacenvReplayLayout L;
+  replay_layout(*p, &L);
+  out->member_bytes = L.total_bytes;
+  out->total_bytes = members * L.total_bytes;
+  out->max_members = kRbPopMax;
+  out->pad = 0;
+  return SACENV_OK;
+}
+
+extern "C" int sacenv_replay_pop_init(const SacenvReplayParams* p, int32_t members, void* arena,
+                                      const uint32_t* seeds, void* stream) {
+  const int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (arena == nullptr || seeds == nullptr) return SACENV_E_NULL;
+  if (!aligned256(arena)) return SACENV_E_SIZE;
+  // One member is one buffer: its launches are the one-buffer kernels (here and in the
+  // three entry points below). The population kernels take more arguments and move every
+  // pointer, which P >= 2 repays and P = 1 would only pay (measured).
+  if (members == 1) return sacenv_replay_init(p, arena, seeds[0], stream);
+  PopSeeds s{};
+  for (int m = 0; m < members; ++m) s.v[m] = seeds[m];
+  const RB r = make_rb(*p, arena);
+  hipLaunchKernelGGL(k_rb_init_pop, dim3(1, members), dim3(kWave), 0, (hipStream_t)stream, r, r.L.total_bytes, s);
+  return status();
+}
+
+extern "C" int sacenv_replay_pop_store(const SacenvReplayParams* p, int32_t members, void* arena, int64_t cntr,
+                                       int64_t n, const float* state, const float* action, const void* reward,
+                                       const float* new_state, const float* final_state, const uint8_t* code,
+                                       uint8_t* last_term, void* stream) {
+  int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (cntr < -1) return SACENV_E_RANGE;
+  if (n < 0) return SACENV_E_SIZE;
+  if (n == 0) return SACENV_OK;
+  if (!arena || !state || !action || !reward || !new_state || !code) return SACENV_E_NULL;
+  if (!aligned256(arena)) return SACENV_E_SIZE;
+  const int64_t rows = n > p->mem_size ? p->mem_size : n;
+  const int64_t total = rows * ((int64_t)p->obs_dim + p->act_dim + 1) + (last_term ? n - rows : 0);
+  if (total >= (1LL << 32)) return SACENV_E_SIZE;  // 32-bit element index per member and call
+  if (members == 1)
+    return cntr >= 0 ? sacenv_replay_store_env_at(p, arena, cntr, n, state, action, reward, new_state, final_state,
+                                                  code, last_term, stream)
+                     : sacenv_replay_store_env(p, arena, n, state, action, reward, new_state, final_state, code,
+                                               last_term, stream);
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  const RB r = make_rb(*p, arena);
+  hipLaunchKernelGGL(k_rb_store_pop, dim3((unsigned)blocks, members), dim3(256), 0, (hipStream_t)stream, *p, r,
+                     r.L.total_bytes, cntr, n, n, state, action, reward, new_state, final_state, code, last_term);
+  if ((rc = status())) return rc;
+  if (cntr >= 0) return SACENV_OK;  // the first workgroup of every member wrote the advanced count
+  hipLaunchKernelGGL(k_rb_advance_pop, dim3(1, members), dim3(kWave), 0, (hipStream_t)stream, r, r.L.total_bytes, n);
+  return status();
+}
+
+extern "C" int sacenv_replay_pop_sample(const SacenvReplayParams* p, int32_t members, void* arena, int32_t batch,
+                                        int64_t stored, int64_t* idx, float* state, float* action, double* reward,
+                                        float* new_state, uint8_t* terminal, void* stream) {
+  int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (batch < 0) return SACENV_E_SIZE;
+  if (stored <= 0) return SACENV_E_SIZE;  // np.random.choice(0, n) raises
+  if (arena == nullptr || idx == nullptr) return SACENV_E_NULL;
+  if (!aligned256(arena) || !batch_fits(p, batch)) return SACENV_E_SIZE;
+  if (batch == 0) return SACENV_OK;
+  if (members == 1)
+    return sacenv_replay_sample(p, arena, batch, stored, idx, state, action, reward, new_state, terminal, stream);
+  const RB r = make_rb(*p, arena);
+  hipLaunchKernelGGL(k_rb_draw_pop, dim3(1, members), dim3(kDrawThreads), 0, (hipStream_t)stream, *p, r,
+                     r.L.total_bytes, batch, idx);
+  if ((rc = status())) return rc;
+  return gather_pop(p, members, r, batch, idx, state, action, reward, new_state, terminal, stream);
+}
+
+extern "C" int sacenv_replay_pop_gather(const SacenvReplayParams* p, int32_t members, void* arena, int32_t batch,
+                                        const int64_t* idx, float* state, float* action, double* reward,
+                                        float* new_state, uint8_t* terminal, void* stream) {
+  const int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (batch < 0) return SACENV_E_SIZE;
+  if (arena == nullptr || idx == nullptr) return SACENV_E_NULL;
+  if (!aligned256(arena) || !batch_fits(p, batch)) return SACENV_E_SIZE;
+  if (batch == 0) return SACENV_OK;
+  if (members == 1)
+    return sacenv_replay_gather(p, arena, batch, idx, state, action, reward, new_state, terminal, stream);
+  return gather_pop(p, members, make_rb(*p, arena), batch, idx, state, action, reward, new_state, terminal, stream);
+}

@@ -9,7 +9,7 @@ from .config import BoatConfig
 from .spaces import Box
 
 __all__ = ["BoatConfig", "Box", "VecBoatEnv", "BoatEnv", "ParachuteEnv", "CarEnv", "VecToyEnv",
-           "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "_lib"]
+           "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "PopulationReplay", "_lib"]
 
 
 def __getattr__(name):  # lazy: importing torch-dependent classes only when used
@@ -25,4 +25,7 @@ def __getattr__(name):  # lazy: importing torch-dependent classes only when used
     if name in ("NativeSACPopulation", "sample_hpsets", "HPRanges"):
         from . import population
         return getattr(population, name)
+    if name == "PopulationReplay":
+        from .population_replay import PopulationReplay
+        return PopulationReplay
     raise AttributeError(name)

@@ -17,7 +17,8 @@ INCLUDE = os.path.join(REPO_ROOT, "include")
 BUILD = os.path.join(PKG_ROOT, "build")
 LIB = os.path.join(BUILD, "libsacenv.so")
 SOURCES = ("sacenv_boat.hip", "sacenv_replay.hip", "sacenv_sac.hip", "sacenv_episodes.hip",
-           "sacenv_sac_pop.hip")   # (includes sacenv_sac.hip for its device bodies)
+           "sacenv_sac_pop.hip",       # (includes sacenv_sac.hip for its device bodies)
+           "sacenv_replay_pop.hip")    # (includes sacenv_replay.hip for its device bodies)
 HEADERS = ("mt19937.h",)
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fPIC", "-shared", "-Wall")
@@ -26,7 +27,8 @@ HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 def deps() -> list[tuple[str, str]]:
     """(path relative to the repo root, absolute path) of every input file."""
     rel = [os.path.join("sac-agent_amd", "csrc", f) for f in SOURCES + HEADERS]
-    rel += [os.path.join("include", h) for h in ("sacenv.h", "sacenv_episodes.h", "sacenv_population.h")]
+    rel += [os.path.join("include", h) for h in ("sacenv.h", "sacenv_episodes.h", "sacenv_population.h",
+                                                    "sacenv_population_replay.h")]
     return [(r, os.path.join(REPO_ROOT, r)) for r in rel]
 
 

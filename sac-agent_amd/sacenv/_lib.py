@@ -194,6 +194,18 @@ class SacPopLayout(C.Structure):
                 ("total_scratch_bytes", _i64), ("max_members", _i32), ("pad", _i32)]
 
 
+# include/sacenv_population_replay.h (SACENV_REPLAY_POP_VERSION 1): the P replay buffers of a
+# population in one set of launches; beside the ABI of sacenv.h, bound only where the library has them
+REPLAY_POP_VERSION = 1
+REPLAY_POP_MAX_MEMBERS = 64
+REPLAY_POP_EXPORTS = ("sacenv_replay_pop_layout", "sacenv_replay_pop_init", "sacenv_replay_pop_store",
+                      "sacenv_replay_pop_sample", "sacenv_replay_pop_gather")
+
+
+class ReplayPopLayout(C.Structure):
+    _fields_ = [("member_bytes", _i64), ("total_bytes", _i64), ("max_members", _i32), ("pad", _i32)]
+
+
 _LIB = None
 
 
@@ -301,6 +313,14 @@ def load(path: str | None = None):
         f = getattr(lib, name, None)   # absent from a library built before sacenv_population.h
         if f is not None:
             f.restype, f.argtypes = C.c_int, args
+    for name, args in zip(REPLAY_POP_EXPORTS, (
+            [RP, _i32, C.POINTER(ReplayPopLayout)], [RP, _i32, _p, C.POINTER(C.c_uint32), _p],
+            [RP, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
+            [RP, _i32, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p],
+            [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])):
+        f = getattr(lib, name, None)   # absent from a library built before sacenv_population_replay.h
+        if f is not None:
+            f.restype, f.argtypes = C.c_int, args
     v = lib.sacenv_abi_version()
     if v != ABI_VERSION:
         raise SacenvError(f"libsacenv ABI {v} != expected {ABI_VERSION}")
@@ -339,6 +359,15 @@ def sac_layout(params: SacParams) -> SacLayout:
 def sac_pop_layout(params: SacParams, members: int) -> SacPopLayout:
     out = SacPopLayout()
     check(load().sacenv_sac_pop_layout(C.byref(params), int(members), C.byref(out)))
+    return out
+
+
+def replay_pop_layout(params: ReplayParams, members: int) -> ReplayPopLayout:
+    lib = load()
+    if not hasattr(lib, "sacenv_replay_pop_layout"):
+        raise SacenvError("this libsacenv.so was built before sacenv_population_replay.h")
+    out = ReplayPopLayout()
+    check(lib.sacenv_replay_pop_layout(C.byref(params), int(members), C.byref(out)))
     return out
 
 

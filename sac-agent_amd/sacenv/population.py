@@ -114,7 +114,8 @@ class NativeSACPopulation:
     """P ``NativeSAC`` agents learning in lockstep, in one set of launches."""
 
     def __init__(self, device, configs, *, obs_dim: int = 11, max_action: float = 1.0, init_seeds=None,
-                 buffer_seeds=None, with_memory: bool = True, adam_eps: float = 1e-8, _build: bool = True):
+                 buffer_seeds=None, with_memory: bool = True, adam_eps: float = 1e-8, replay=None,
+                 _build: bool = True):
         cfgs = _common_configs(configs)
         P = self.P = len(cfgs)
         cfg = cfgs[0]
@@ -129,6 +130,17 @@ class NativeSACPopulation:
         if dev.type != "cuda":
             raise _lib.SacenvError("NativeSACPopulation runs on the GPU only (libsacenv SAC kernels)")
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        if replay is not None:
+            # one PopulationReplay for all members (sacenv/population_replay.py): checked before
+            # anything is built or launched
+            from .population_replay import PopulationReplay
+            if not isinstance(replay, PopulationReplay):
+                raise TypeError("replay must be a PopulationReplay")
+            for what, have, want in (("members", replay.P, P), ("max_size", replay.mem_size, cfg.max_size),
+                                     ("obs_dim", replay.params.obs_dim, obs_dim), ("n_actions", replay.n_actions, 1),
+                                     ("device", replay.device, self.device)):
+                if have != want:
+                    raise ValueError(f"the replay's {what} ({have}) must be the population's ({want})")
         self.configs = cfgs
         # the fields the members share; lr_*, gamma, tau and reward_scale here are member 0's and
         # are not read by the population entry points (they take self._hp)
@@ -151,7 +163,10 @@ class NativeSACPopulation:
         if _build:
             self.sync()
         self.memory = None
-        if with_memory:
+        self._pop_replay = replay is not None
+        if replay is not None:
+            self.memory = replay
+        elif with_memory:
             from .replay import DeviceReplayBuffer
             self.memory = [DeviceReplayBuffer(cfg.max_size, (obs_dim,), 1, device=self.device,
                                               seed=m if buffer_seeds is None else buffer_seeds[m])
@@ -197,14 +212,21 @@ class NativeSACPopulation:
         return out
 
     def remember(self, m: int, state, action, reward, new_state, code, **kw) -> None:
-        """``memory[m].store_batch``: member m's transitions."""
+        """``memory[m].store_batch``: member m's transitions. (With a ``PopulationReplay`` the
+        members store in lockstep, through the replay itself.)"""
+        if self._pop_replay:
+            raise TypeError("this population holds a PopulationReplay, whose members store in lockstep: use "
+                            "memory.store_batch / memory.store_env_step for all members at once")
         self.memory[m].store_batch(state, action, reward, new_state, code, **kw)
 
     store_batch = remember
 
     def sample(self):
-        """One batch per member from its own buffer, stacked as ``learn`` takes them."""
+        """One batch per member from its own buffer, as ``learn`` takes them: stacked, or with a
+        ``PopulationReplay`` as its two launches write them."""
         B = self.configs[0].batch_size
+        if self._pop_replay:
+            return self.memory.sample(B, as_bool=False)[:5]
         rows = [mem.sample(B, as_bool=False)[:5] for mem in self.memory]
         return tuple(torch.stack([r[k] for r in rows]) for k in range(5))
 
@@ -212,12 +234,15 @@ class NativeSACPopulation:
     def learn(self, batch=None, noise=None, *, losses: bool = True):
         """``NativeSAC.learn`` for every member. ``batch`` = stacked (state [P, B, D], action
         [P, B, 1], reward [P, B], new_state, done); else each member's own buffer is sampled
-        (None until every buffer holds B rows). ``noise`` = (eps1, eps2), each [P, B(, 1)].
+        (None until every buffer holds B rows; a ``PopulationReplay`` given as ``replay=`` is
+        sampled in two launches, with no stacking). ``noise`` = (eps1, eps2), each [P, B(, 1)].
         Returns a [P, 4] tensor of (value, actor, critic 1, critic 2) losses: a copy, or with
         ``losses=False`` the population's own buffer, which the next learn() rewrites."""
         P, B, D = self.P, self.configs[0].batch_size, self.params.obs_dim
         if batch is None:
-            if self.memory is None or any(mem.mem_cntr < B for mem in self.memory):
+            if self.memory is None:
+                return None
+            if self.memory.mem_cntr < B if self._pop_replay else any(mem.mem_cntr < B for mem in self.memory):
                 return None
             batch = self.sample()
         state, action, reward, state_, done = batch
