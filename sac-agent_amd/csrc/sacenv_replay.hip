@@ -11,147 +11,19 @@
 //
 // The buffer's arrays are row-major per transition (the policy reads whole
 // rows); the store is coalesced along the flattened row-major element index.
+//
+// The layout, the bodies of the five one-buffer kernels and the host rules that the
+// population unit (sacenv_replay_pop.hip) applies too are in sacenv_replay_core.h; this
+// file holds the kernels -- the wrappers of those bodies, and the staged sampler's, the
+// side launch's and the stand-in's, which are its own -- and the entry points of
+// include/sacenv.h.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "sacenv.h"
+#include "sacenv_replay_core.h"
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kMtN = SACENV_MT_N;
-constexpr int kMtM = 397;
-constexpr uint32_t kMtUpper = 0x80000000u;
-constexpr uint32_t kMtLower = 0x7fffffffu;
-constexpr uint32_t kMtMatrixA = 0x9908b0dfu;
-
-#include "mt19937.h"
-
-__host__ __device__ inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
-
-__host__ __device__ inline void replay_layout(const SacenvReplayParams& p, SacenvReplayLayout* o) {
-  const int64_t M = p.mem_size;
-  int64_t off = 0;
-  o->state = off;
-  off = align256(off + 4 * M * p.obs_dim);
-  o->new_state = off;
-  off = align256(off + 4 * M * p.obs_dim);
-  o->action = off;
-  off = align256(off + 4 * M * p.act_dim);
-  o->reward = off;
-  off = align256(off + 8 * M);
-  o->terminal = off;
-  off = align256(off + M);
-  o->mem_cntr = off;
-  off += 256;
-  o->mt_key = off;
-  off = align256(off + 4 * kMtN);
-  o->mt_pos = off;
-  off += 256;
-  o->total_bytes = off;
-}
-
-struct RB {
-  char* b;
-  SacenvReplayLayout L;
-  __device__ float* state() const { return reinterpret_cast<float*>(b + L.state); }
-  __device__ float* new_state() const { return reinterpret_cast<float*>(b + L.new_state); }
-  __device__ float* action() const { return reinterpret_cast<float*>(b + L.action); }
-  __device__ double* reward() const { return reinterpret_cast<double*>(b + L.reward); }
-  __device__ uint8_t* terminal() const { return reinterpret_cast<uint8_t*>(b + L.terminal); }
-  __device__ int64_t* cntr() const { return reinterpret_cast<int64_t*>(b + L.mem_cntr); }
-  __device__ uint32_t* key() const { return reinterpret_cast<uint32_t*>(b + L.mt_key); }
-  __device__ int32_t* pos() const { return reinterpret_cast<int32_t*>(b + L.mt_pos); }
-};
-
-// The bodies of the five one-buffer kernels are device functions: sacenv_replay_pop.hip
-// includes this file with SACENV_REPLAY_BODIES_ONLY (the kernels and entry points compiled
-// out) and runs them under a second grid dimension over the members of a population. They
-// index by blockIdx.x / gridDim.x only.
-__device__ __forceinline__ void init_body(const RB& r, uint32_t seed) {
-  if (threadIdx.x != 0) return;
-  uint32_t x = seed;  // init_genrand (numpy RandomState._legacy_seeding)
-  for (int i = 0; i < kMtN; ++i) {
-    r.key()[i] = x;
-    x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)(i + 1);
-  }
-  *r.pos() = kMtN;
-  *r.cntr() = 0;
-}
-
-#ifndef SACENV_REPLAY_BODIES_ONLY  // sacenv_replay_pop.hip includes this file for the device bodies and host helpers alone
 __global__ void __launch_bounds__(kWave) k_rb_init(RB r, uint32_t seed) { init_body(r, seed); }
-#endif  // SACENV_REPLAY_BODIES_ONLY
 
-// store_transition for rows [0, n): row i -> (mem_cntr + i) % M. Rows that a
-// later row of the same call overwrites (i < n - M) are skipped, so the ring
-// ends exactly as n sequential calls leave it. Element-parallel over the
-// (n - first) x (D + A + 1) stored columns with 32-bit index math. mem_cntr
-// advances in a second launch (k_rb_advance), after every workgroup has read
-// it: stream order instead of a grid-wide atomic (one word takes ~90
-// returning atomics/µs) or an agent-scope acq_rel fence per workgroup. With the
-// count from the host (host_cntr >= 0) no workgroup reads it, so the first one
-// writes the advanced count and the second launch goes (one fixed launch cost,
-// ~5 us, per stored step).
-__device__ __forceinline__ void store_body(const SacenvReplayParams& p, const RB& r, int64_t host_cntr,
-                                           int64_t advance, int64_t n, int64_t offset,
-                                           const float* __restrict__ state, const float* __restrict__ action,
-                                           const void* __restrict__ reward, const float* __restrict__ new_state,
-                                           const float* __restrict__ final_state, const uint8_t* __restrict__ code,
-                                           uint8_t* __restrict__ last_term) {
-  const int64_t M = p.mem_size, c0 = (host_cntr >= 0 ? host_cntr : *r.cntr()) + offset;
-  if (host_cntr >= 0 && blockIdx.x == 0 && threadIdx.x == 0) *r.cntr() = host_cntr + advance;  // buffer.py:22
-  const int64_t first = n > M ? n - M : 0;
-  const uint32_t rows = (uint32_t)(n - first);
-  const uint32_t base = (uint32_t)((c0 + first) % M);  // ring row of stored row 0
-  const uint32_t D = (uint32_t)p.obs_dim, A = (uint32_t)p.act_dim, Mu = (uint32_t)M;
-  const uint32_t nD = rows * D, nA = rows * A, stored = nD + nA + rows;
-  // with last_term, rows a later row overwrites still update their env's byte
-  const uint32_t total = stored + (last_term != nullptr ? (uint32_t)first : 0u);
-  for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < total; q += gridDim.x * blockDim.x) {
-    if (q < nD) {
-      const uint32_t j = q / D, k = q - j * D;
-      uint32_t row = base + j;
-      row = row >= Mu ? row - Mu : row;
-      const int64_t src = (first + j) * (int64_t)D + k;
-      r.state()[(int64_t)row * D + k] = state[src];
-      const float* ns = (final_state != nullptr && code[first + j] != 0) ? final_state : new_state;
-      r.new_state()[(int64_t)row * D + k] = ns[src];
-    } else if (q < nD + nA) {
-      const uint32_t qq = q - nD, j = qq / A, k = qq - j * A;
-      uint32_t row = base + j;
-      row = row >= Mu ? row - Mu : row;
-      r.action()[(int64_t)row * A + k] = action[(first + j) * (int64_t)A + k];
-    } else if (q < stored) {
-      const uint32_t j = q - nD - nA;
-      uint32_t row = base + j;
-      row = row >= Mu ? row - Mu : row;
-      const int64_t i = first + j;
-      r.reward()[row] = p.reward_f32 ? (double)static_cast<const float*>(reward)[i]
-                                     : static_cast<const double*>(reward)[i];
-      uint32_t cd = code[i];
-      if (last_term != nullptr) {
-        // main.py:83 tests info['termination'], which only the termination
-        // chain writes (boat_env.py:84-105) and reset never clears (:120-126):
-        // codes 1..5 overwrite env i's last termination, others keep it
-        if (cd >= 1u && cd <= 5u) last_term[i] = (uint8_t)cd;
-        else cd = last_term[i];
-      }
-      r.terminal()[row] = (uint8_t)((p.terminal_mask >> (cd < 31 ? cd : 31)) & 1u);
-    } else {
-      const int64_t i = q - stored;  // a row the ring drops: only its env's byte
-      const uint32_t cd = code[i];
-      if (cd >= 1u && cd <= 5u) last_term[i] = (uint8_t)cd;
-    }
-  }
-}
-
-__device__ __forceinline__ void advance_body(const RB& r, int64_t n) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *r.cntr() += n;  // buffer.py:22
-}
-
-#ifndef SACENV_REPLAY_BODIES_ONLY
 __global__ void __launch_bounds__(256) k_rb_store(SacenvReplayParams p, RB r, int64_t host_cntr, int64_t advance,
                                                   int64_t n, int64_t offset,
                                                   const float* __restrict__ state,
@@ -165,209 +37,14 @@ __global__ void __launch_bounds__(256) k_rb_store(SacenvReplayParams p, RB r, in
 }
 
 __global__ void k_rb_advance(RB r, int64_t n) { advance_body(r, n); }
-#endif  // SACENV_REPLAY_BODIES_ONLY
 
-// np.random.choice(max_mem, batch) with replace=True, p=None: numpy legacy
-// randint(0, max_mem) -> masked rejection on 32-bit words (rng = max_mem-1;
-// rng == 0 draws nothing); words in order, accepted words fill the batch in
-// order, the stream stops after the batch-th accepted word: k_rb_draw_many below
-// (one 1 024-thread workgroup).
-
-// Sharded rows (sacenv_replay_sample_shard): ring row p holds the transition
-// with the latest global sequence number s <= mem_cntr - 1, s = p (mod M); this
-// shard wrote it iff (s mod period) is in [lo, hi). Rows of other shards come
-// out as zero bits.
-struct Shard {
-  int64_t period, lo, hi;  // period 0: every row is this shard's
-};
-__device__ __forceinline__ bool owns(const Shard& sh, int64_t cnt, int64_t M, int64_t row) {
-  if (sh.period == 0) return true;
-  const int64_t s = row + M * ((cnt - 1 - row) / M);
-  const int64_t u = s % sh.period;
-  return u >= sh.lo && u < sh.hi;
-}
-
-__device__ __forceinline__ void gather_body(const SacenvReplayParams& p, const RB& r, int batch,
-                                            const int64_t* __restrict__ idx, float* __restrict__ st,
-                                            float* __restrict__ ac, double* __restrict__ rw,
-                                            float* __restrict__ ns, uint8_t* __restrict__ tm, const Shard& sh) {
-  const int D = p.obs_dim, A = p.act_dim;
-  const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t nd = (int64_t)batch * D, na = (int64_t)batch * A;
-  const int64_t cnt = *r.cntr(), M = p.mem_size;
-  // (an index outside the ring -- a caller's, sacenv_replay_gather -- reads nothing: zero bits)
-  if (q < nd) {
-    const int64_t i = q / D, k = q - i * D, row = idx[i];
-    const bool own = row >= 0 && row < M && owns(sh, cnt, M, row);
-    if (st) st[q] = own ? r.state()[row * D + k] : 0.f;
-    if (ns) ns[q] = own ? r.new_state()[row * D + k] : 0.f;
-  } else if (q < nd + na) {
-    const int64_t qq = q - nd, i = qq / A, k = qq - i * A, row = idx[i];
-    if (ac) ac[qq] = row >= 0 && row < M && owns(sh, cnt, M, row) ? r.action()[row * A + k] : 0.f;
-  } else if (q < nd + na + batch) {
-    const int64_t i = q - nd - na, row = idx[i];
-    const bool own = row >= 0 && row < M && owns(sh, cnt, M, row);
-    if (rw) rw[i] = own ? r.reward()[row] : 0.0;
-    if (tm) tm[i] = own ? r.terminal()[row] : (uint8_t)0;
-  }
-}
-
-#ifndef SACENV_REPLAY_BODIES_ONLY
 __global__ void __launch_bounds__(256) k_rb_gather(SacenvReplayParams p, RB r, int batch,
                                                    const int64_t* __restrict__ idx, float* __restrict__ st,
                                                    float* __restrict__ ac, double* __restrict__ rw,
                                                    float* __restrict__ ns, uint8_t* __restrict__ tm, Shard sh) {
   gather_body(p, r, batch, idx, st, ac, rw, ns, tm, sh);
 }
-#endif  // SACENV_REPLAY_BODIES_ONLY
 
-// ---------------------------------------------------------------------------
-// The staged sampler: the pooled buffer of main.py:78-90 -- every rank's envs
-// storing one transition each per step, one learn() (sample_buffer,
-// buffer.py:24-35) after every step -- sampled out of the rows the persistent
-// step launch wrote (sacenv_boat_segment's `stage`), with no ring. A ring of M
-// rows that takes `period` rows per step holds the last M sequence numbers;
-// with M <= seg * period every row learn k of segment g can reach (and the row
-// before it, for s) lies in segment g or g - 1, so two staged segments ARE the
-// ring. The index draws depend only on the sampling stream and the counts
-// stored, so segment g's are drawn before it steps, and the launch writes only
-// the rows some learn will read (sacenv_replay_stage_mark).
-
-struct StagedGeom {
-  int64_t period, offset, g;
-  int n, n_pad, seg, exp2;
-  double r_mem, r_period;  // 1 / mem_size, 1 / period (host IEEE divisions)
-};
-
-// floor(x / d) for 0 <= x < 2^52 and 0 < d < 2^31 from the rounded reciprocal rd:
-// the double estimate is off by at most one, fixed by one step each way (a 64-bit
-// integer division is a ~50-instruction sequence on the GPU)
-__device__ __forceinline__ int64_t div_floor(int64_t x, int64_t d, double rd) {
-  int64_t q = (int64_t)((double)x * rd);
-  q -= q * d > x ? 1 : 0;
-  q += (q + 1) * d <= x ? 1 : 0;
-  return q;
-}
-
-// The staged segment buffers are ENV-MAJOR (round 6): env e's 64-B row of step j of a
-// segment at (e x seg + j) x 64, its mark bits in the ceil(seg / 64) words from e x
-// that, bit j % 64 -- a row and its predecessor (the row before it: its s) share a
-// mark word (one atomic) and mostly a 128-B line.
-__device__ __forceinline__ int64_t stage_row(const StagedGeom& G, int e, int64_t j) {
-  return ((int64_t)e * G.seg + j) * 64;
-}
-__device__ __forceinline__ void mark_rows(unsigned long long* __restrict__ marks, const StagedGeom& G, int e,
-                                          int64_t j, unsigned long long bits) {
-  const int W = (G.seg + 63) / 64;
-  atomicOr(&marks[(int64_t)e * W + (j >> 6)], bits << (j & 63));
-}
-
-// ring row `row` at learn time (cntr rows stored) -> (global step q, global env u)
-__device__ __forceinline__ void resolve(int64_t row, int64_t cntr, int64_t M, const StagedGeom& G, int64_t* q,
-                                        int64_t* u) {
-  // the latest sequence number = row (mod M) below cntr
-  const int64_t s = row + M * div_floor(cntr - 1 - row, M, G.r_mem);
-  *q = div_floor(s, G.period, G.r_period);
-  *u = s - *q * G.period;
-}
-
-// n_batches consecutive np.random.choice(min(cntr_k, M), batch) calls on one
-// stream, cntr_k = cntr0 + (k + 1) * period (learn k follows step k's stores),
-// learns with cntr_k < batch skipped (continuous_agent.py:97-98: idx = -1, no
-// words). The general path (ranges that change between learns): one workgroup;
-// a whole 624-word block is tempered and tested at once (thread i: word i),
-// accepted words are ranked with a ballot per wave and a prefix over the
-// waves; a batch that completes inside the block ends at its last accepted
-// word, and the next batch re-tests the block from there.
-constexpr int kDrawThreads = 1024;
-__device__ __forceinline__ void mt_twist_block(const uint32_t* __restrict__ o, uint32_t* __restrict__ n, int tid) {
-  constexpr int kD = kMtN - kMtM;  // 227
-  if (tid < kD) n[tid] = mt_mix(o[tid], o[tid + 1], o[tid + kMtM]);
-  __syncthreads();
-  if (tid < kD) n[kD + tid] = mt_mix(o[kD + tid], o[kD + tid + 1], n[tid]);
-  __syncthreads();
-  if (tid < kMtN - 1 - 2 * kD) n[2 * kD + tid] = mt_mix(o[2 * kD + tid], o[2 * kD + tid + 1], n[kD + tid]);
-  __syncthreads();
-  if (tid == 0) n[kMtN - 1] = mt_mix(o[kMtN - 1], n[0], n[kMtM - 1]);
-  __syncthreads();
-}
-
-// kSample: one sample_buffer(batch) at the device count (sacenv_replay_sample: no
-// learn() skip below batch rows; graph-capturable like the store), else the nb
-// learns of a staged segment at counts cntr0 + (k + 1) * period.
-template <bool kSample>
-__device__ __forceinline__ void draw_many_body(const SacenvReplayParams& p, const RB& r, int batch, int nb,
-                                               int64_t cntr0, int64_t period, int64_t* __restrict__ idx) {
-  __shared__ uint32_t blk[2][kMtN];
-  __shared__ int wcnt[kDrawThreads / kWave];
-  __shared__ int s_end;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  constexpr int kWaves = kDrawThreads / kWave;
-  int cur = 0, pos = *r.pos();
-  if (pos < 0) {  // a poisoned stream (a staged draw ran short): draw nothing, keep the poison
-    for (int64_t i = tid; i < (int64_t)nb * batch; i += kDrawThreads) idx[i] = -1;
-    return;
-  }
-  for (int i = tid; i < kMtN; i += kDrawThreads) blk[0][i] = r.key()[i];
-  bool advanced = false;
-  __syncthreads();
-  int k = 0, filled = 0;
-  while (k < nb) {
-    const int64_t c = kSample ? *r.cntr() : cntr0 + (int64_t)(k + 1) * period;
-    const int64_t max_mem = c < p.mem_size ? c : p.mem_size;
-    const uint32_t rng = (uint32_t)(max_mem - 1);
-    const bool skip = !kSample && c < batch;
-    if (skip || rng == 0u) {  // learn() returns before sampling, or numpy's off + 0: no words
-      for (int i = tid; i < batch; i += kDrawThreads) idx[(int64_t)k * batch + i] = skip ? -1 : 0;
-      ++k;
-      continue;
-    }
-    uint32_t mask = rng;
-    mask |= mask >> 1;
-    mask |= mask >> 2;
-    mask |= mask >> 4;
-    mask |= mask >> 8;
-    mask |= mask >> 16;
-    if (pos >= kMtN) {
-      mt_twist_block(blk[cur], blk[cur ^ 1], tid);
-      cur ^= 1;
-      pos = 0;
-      advanced = true;
-    }
-    const bool valid = tid >= pos && tid < kMtN;
-    const uint32_t w = valid ? (mt_temper(blk[cur][tid]) & mask) : 0u;
-    const bool acc = valid && w <= rng;
-    const unsigned long long bal = __ballot(acc);
-    if (lane == 0) wcnt[wv] = __popcll(bal);
-    __syncthreads();
-    int excl = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < kWaves; ++q) {
-      const int v = wcnt[q];
-      excl += q < wv ? v : 0;
-      total += v;
-    }
-    const int rank = excl + __popcll(bal & ((1ull << lane) - 1ull));
-    const int take = batch - filled;
-    if (acc && rank < take) idx[(int64_t)k * batch + filled + rank] = (int64_t)w;
-    if (total >= take) {  // the take-th accepted word ends batch k
-      if (acc && rank == take - 1) s_end = tid;
-      __syncthreads();
-      pos = s_end + 1;
-      ++k;
-      filled = 0;
-    } else {
-      filled += total;
-      pos = kMtN;
-    }
-    __syncthreads();  // wcnt / s_end are rewritten by the next round
-  }
-  if (advanced)
-    for (int i = tid; i < kMtN; i += kDrawThreads) r.key()[i] = blk[cur][i];
-  if (tid == 0) *r.pos() = pos;
-}
-
-#ifndef SACENV_REPLAY_BODIES_ONLY  // (down to the host helpers: the staged, side and stand-in kernels)
 template <bool kSample = false>
 __global__ void __launch_bounds__(kDrawThreads) k_rb_draw_many(SacenvReplayParams p, RB r, int batch, int nb,
                                                                int64_t cntr0, int64_t period,
@@ -723,7 +400,8 @@ __device__ __forceinline__ int64_t ctr_draw4(uint64_t seed, int64_t L, int i, ui
   return v <= rng ? (int64_t)v : 0;
 }
 
-__device__ __forceinline__ uint64_t range_mask(uint64_t rng) {
+// the smallest 2^k - 1 >= rng: numpy's masked rejection tests a word's bits under it
+__host__ __device__ __forceinline__ uint64_t range_mask(uint64_t rng) {
   uint64_t m = rng;
   m |= m >> 1;
   m |= m >> 2;
@@ -1087,30 +765,9 @@ __global__ void __launch_bounds__(256) k_copy_standin(const uint4* __restrict__ 
 
 // 32-bit words of one learn's batch in sacenv_replay_sample_staged's packing
 int64_t words_per_batch(int32_t batch) { return (int64_t)batch * (2 * SACENV_OBS_DIM + 1 + 3); }
-#endif  // SACENV_REPLAY_BODIES_ONLY
-
-int check_replay(const SacenvReplayParams* p) {
-  if (p == nullptr) return SACENV_E_NULL;
-  if (p->mem_size <= 0 || p->mem_size > 0x7FFFFFFFLL || p->obs_dim <= 0 || p->act_dim <= 0)
-    return SACENV_E_SIZE;  // 32-bit ring rows; randint on 32-bit words
-  return SACENV_OK;
-}
-
-RB make_rb(const SacenvReplayParams& p, void* arena) {
-  RB r;
-  r.b = static_cast<char*>(arena);
-  replay_layout(p, &r.L);
-  return r;
-}
-
-int status() {
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? SACENV_OK : (int)err;
-}
 
 }  // namespace
 
-#ifndef SACENV_REPLAY_BODIES_ONLY  // sacenv_replay_pop.hip includes this file for the device bodies and host helpers alone
 extern "C" {
 
 int sacenv_replay_layout(const SacenvReplayParams* p, SacenvReplayLayout* out) {
@@ -1139,11 +796,8 @@ static int store(const SacenvReplayParams* p, void* arena, int64_t n, int64_t of
   if (host_cntr >= 0 && n == 0) host_cntr = -1;  // nothing to launch: advance as before
   if (n == 0 && advance == n) return SACENV_OK;
   if (!arena || !state || !action || !reward || !new_state || !code) return SACENV_E_NULL;
-  const int64_t rows = n > p->mem_size ? p->mem_size : n;
-  const int64_t total = rows * ((int64_t)p->obs_dim + p->act_dim + 1) + (last_term ? n - rows : 0);
-  if (total >= (1LL << 32)) return SACENV_E_SIZE;  // 32-bit element index per call
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
+  int64_t blocks;
+  if ((rc = store_grid(p, n, last_term, &blocks))) return rc;
   const RB r = make_rb(*p, arena);
   if (n > 0) {
     hipLaunchKernelGGL(k_rb_store, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *p, r, host_cntr,
@@ -1188,10 +842,7 @@ static int sample(const SacenvReplayParams* p, void* arena, int32_t batch, int64
                   float* state, float* action, double* reward, float* new_state, uint8_t* terminal,
                   const Shard& sh, void* stream) {
   int rc = check_replay(p);
-  if (rc) return rc;
-  if (batch < 0) return SACENV_E_SIZE;
-  if (stored <= 0) return SACENV_E_SIZE;  // np.random.choice(0, n) raises
-  if (arena == nullptr || idx == nullptr) return SACENV_E_NULL;
+  if (rc || (rc = check_batch_call(arena, idx, batch, stored))) return rc;
   if (batch == 0) return SACENV_OK;
   const RB r = make_rb(*p, arena);
   // one 1 024-thread workgroup: a twist per 624 words and one ballot-and-scan round per
@@ -1199,9 +850,8 @@ static int sample(const SacenvReplayParams* p, void* arena, int32_t batch, int64
   hipLaunchKernelGGL(k_rb_draw_many<true>, dim3(1), dim3(kDrawThreads), 0, (hipStream_t)stream, *p, r, batch, 1,
                      (int64_t)0, (int64_t)0, idx);
   if ((rc = status())) return rc;
-  const int64_t total = (int64_t)batch * (p->obs_dim + p->act_dim + 1);
-  hipLaunchKernelGGL(k_rb_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *p,
-                     r, batch, idx, state, action, reward, new_state, terminal, sh);
+  hipLaunchKernelGGL(k_rb_gather, dim3(gather_blocks(p, batch)), dim3(256), 0, (hipStream_t)stream, *p, r, batch,
+                     idx, state, action, reward, new_state, terminal, sh);
   return status();
 }
 
@@ -1220,7 +870,9 @@ int sacenv_replay_sample_shard(const SacenvReplayParams* p, void* arena, int32_t
                 Shard{period, offset, offset + n}, stream);
 }
 
-static int check_staged(const SacenvReplayParams* p, const SacenvStagedParams* sp) {
+// the staged geometry, then a call's shape: segment g's n_batches learns of `batch` rows
+static int check_staged(const SacenvReplayParams* p, const SacenvStagedParams* sp, int64_t g, int32_t batch,
+                        int32_t n_batches) {
   int rc = check_replay(p);
   if (rc) return rc;
   if (sp == nullptr) return SACENV_E_NULL;
@@ -1229,6 +881,7 @@ static int check_staged(const SacenvReplayParams* p, const SacenvStagedParams* s
   if (sp->offset < 0 || sp->period <= 0 || sp->offset + sp->n > sp->period) return SACENV_E_RANGE;
   // every row a learn can reach (and the row before it) lies in this segment or the previous one
   if (p->mem_size > (int64_t)sp->seg * sp->period) return SACENV_E_RANGE;
+  if (g < 0 || batch < 0 || n_batches < 0 || n_batches > sp->seg) return SACENV_E_SIZE;
   return SACENV_OK;
 }
 
@@ -1252,15 +905,39 @@ static StagedGeom geom(const SacenvReplayParams* p, const SacenvStagedParams* sp
   return G;
 }
 
+// rank 0 (the rank of env 0) packs the all-zero rows of skipped learns
+static int skip_owner(const SacenvStagedParams* sp) { return sp->offset == 0 ? 1 : 0; }
+
+static StagedRows staged_rows(const SacenvStagedParams* sp, const void* cur, const void* prev) {
+  StagedRows S;
+  S.cur = static_cast<const char*>(cur);
+  S.prev = static_cast<const char*>(prev);
+  for (int k = 0; k < SACENV_OBS_DIM; ++k) S.first[k] = sp->first_obs[k];
+  return S;
+}
+
+// the staged rows are read as float4, a chunk as 32-bit words
+static bool stage_ptrs_ok(const void* cur, const void* prev, const void* chunk = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(prev)) & 15u) == 0u &&
+         (reinterpret_cast<uintptr_t>(chunk) & 3u) == 0u;
+}
+
+// the unpack's sizes: 31-bit slot and record numbers, chunks that hold `cap` records, 32-bit
+// words offsets (unpack_tile's meta)
+static bool unpack_fits(int32_t world, int64_t chunk_bytes, int64_t cap, int32_t batch, int32_t n_batches) {
+  if (world < 1 || cap < 0 || batch < 0 || n_batches < 0) return false;
+  if ((int64_t)batch * n_batches >= ((int64_t)1 << 31) || (int64_t)world * cap >= ((int64_t)1 << 31)) return false;
+  if (chunk_bytes < 4 * (kChunkHdr + cap * kRecWords) || (chunk_bytes & 3) != 0) return false;
+  return (int64_t)n_batches * words_per_batch(batch) < ((int64_t)1 << 32);
+}
+
 // the steady-state draw's generated blocks: enough for n_batches * batch accepted
 // words with a 5 % margin over the expected count (at 262 144 draws of [0, 10^6)
 // the count's standard deviation is 0.04 % of it: 120 sigma), + 3 blocks for the
 // start position and small draws
 static int64_t draw_blocks(const SacenvReplayParams* p, int32_t batch, int32_t n_batches) {
   const uint64_t rng = (uint64_t)(p->mem_size - 1);
-  uint64_t mask = rng;
-  for (int sh = 1; sh < 64; sh <<= 1) mask |= mask >> sh;
-  const double acc = (double)(rng + 1) / (double)(mask + 1);
+  const double acc = (double)(rng + 1) / (double)(range_mask(rng) + 1);
   const double need = (double)batch * n_batches;
   return (int64_t)(need / acc * 1.05 / kMtN) + 3;
 }
@@ -1285,9 +962,8 @@ int sacenv_replay_stage_scratch_bytes(const SacenvReplayParams* p, int32_t batch
 int sacenv_replay_stage_draw(const SacenvReplayParams* p, void* arena, const SacenvStagedParams* sp, int64_t g,
                              int32_t batch, int32_t n_batches, int64_t* idx, void* scratch, int64_t scratch_size,
                              void* stream) {
-  int rc = check_staged(p, sp);
+  int rc = check_staged(p, sp, g, batch, n_batches);
   if (rc) return rc;
-  if (g < 0 || batch < 0 || n_batches < 0 || n_batches > sp->seg) return SACENV_E_SIZE;
   if (!arena || !idx) return SACENV_E_NULL;
   if (batch == 0 || n_batches == 0) return SACENV_OK;
   if (!staged_range_ok(sp, g)) return SACENV_E_RANGE;
@@ -1310,9 +986,7 @@ int sacenv_replay_stage_draw(const SacenvReplayParams* p, void* arena, const Sac
   d.tile_off = reinterpret_cast<int*>(sc + align256(4 * K * kMtN) + align256(4 * T));
   d.ctrl = reinterpret_cast<int*>(sc + align256(4 * K * kMtN) + 2 * align256(4 * T));
   d.rng = (uint32_t)(M - 1);
-  uint32_t mask = d.rng;
-  for (int sh = 1; sh < 32; sh <<= 1) mask |= mask >> sh;
-  d.mask = mask;
+  d.mask = (uint32_t)range_mask(d.rng);
   d.need = (int64_t)batch * n_batches;
   d.p0 = -1;       // (read by the kernels from ctrl[3], which k_mt_chain sets)
   d.n_words = -1;
@@ -1331,9 +1005,8 @@ int sacenv_replay_stage_draw(const SacenvReplayParams* p, void* arena, const Sac
 int sacenv_replay_stage_mark(const SacenvReplayParams* p, const SacenvStagedParams* sp, int64_t g,
                              const int64_t* idx_g, const int64_t* idx_next, int32_t batch, int32_t n_batches,
                              uint64_t* marks, void* stream) {
-  int rc = check_staged(p, sp);
+  int rc = check_staged(p, sp, g, batch, n_batches);
   if (rc) return rc;
-  if (g < 0 || batch < 0 || n_batches < 0 || n_batches > sp->seg) return SACENV_E_SIZE;
   if (!idx_g || !marks) return SACENV_E_NULL;
   if (!staged_range_ok(sp, g)) return SACENV_E_RANGE;
   const hipError_t e = hipMemsetAsync(marks, 0, (size_t)sp->n_pad * ((sp->seg + 63) / 64) * 8, (hipStream_t)stream);
@@ -1351,43 +1024,33 @@ int sacenv_replay_stage_mark(const SacenvReplayParams* p, const SacenvStagedPara
 int sacenv_replay_sample_staged(const SacenvReplayParams* p, const SacenvStagedParams* sp, int64_t g,
                                 const void* stage_cur, const void* stage_prev, const int64_t* idx, int32_t batch,
                                 int32_t n_batches, uint32_t* words, void* stream) {
-  int rc = check_staged(p, sp);
+  int rc = check_staged(p, sp, g, batch, n_batches);
   if (rc) return rc;
-  if (g < 0 || batch < 0 || n_batches < 0 || n_batches > sp->seg) return SACENV_E_SIZE;
   if (!stage_cur || !stage_prev || !idx || !words) return SACENV_E_NULL;
   if (!staged_range_ok(sp, g)) return SACENV_E_RANGE;
-  if (((reinterpret_cast<uintptr_t>(stage_cur) | reinterpret_cast<uintptr_t>(stage_prev)) & 15u) != 0u)
-    return SACENV_E_RANGE;
+  if (!stage_ptrs_ok(stage_cur, stage_prev)) return SACENV_E_RANGE;
   if (batch == 0 || n_batches == 0) return SACENV_OK;
-  StagedRows S;
-  S.cur = static_cast<const char*>(stage_cur);
-  S.prev = static_cast<const char*>(stage_prev);
-  for (int k = 0; k < SACENV_OBS_DIM; ++k) S.first[k] = sp->first_obs[k];
   const int64_t total = (int64_t)batch * n_batches;
-  const int64_t per = (int64_t)batch * (2 * SACENV_OBS_DIM + 1 + 3);
   hipLaunchKernelGGL(k_rb_gather_staged, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     *p, geom(p, sp, g), S, batch, n_batches, idx, words, per);
+                     *p, geom(p, sp, g), staged_rows(sp, stage_cur, stage_prev), batch, n_batches, idx, words,
+                     words_per_batch(batch));
   return status();
 }
 
 int sacenv_replay_gather(const SacenvReplayParams* p, void* arena, int32_t batch, const int64_t* idx, float* state,
                          float* action, double* reward, float* new_state, uint8_t* terminal, void* stream) {
   int rc = check_replay(p);
-  if (rc) return rc;
-  if (batch < 0) return SACENV_E_SIZE;
-  if (arena == nullptr || idx == nullptr) return SACENV_E_NULL;
+  if (rc || (rc = check_batch_call(arena, idx, batch))) return rc;
   if (batch == 0) return SACENV_OK;
-  const int64_t total = (int64_t)batch * (p->obs_dim + p->act_dim + 1);
-  hipLaunchKernelGGL(k_rb_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *p,
+  hipLaunchKernelGGL(k_rb_gather, dim3(gather_blocks(p, batch)), dim3(256), 0, (hipStream_t)stream, *p,
                      make_rb(*p, arena), batch, idx, state, action, reward, new_state, terminal, Shard{0, 0, 0});
   return status();
 }
 
 static int check_ctr_shape(const SacenvReplayParams* p, const SacenvStagedParams* sp, int64_t g, int32_t batch,
                            int32_t n_batches) {
-  const int rc = check_staged(p, sp);
+  const int rc = check_staged(p, sp, g, batch, n_batches);
   if (rc) return rc;
-  if (g < 0 || batch < 0 || n_batches < 0 || n_batches > sp->seg) return SACENV_E_SIZE;
   if ((int64_t)batch * n_batches >= ((int64_t)1 << 31)) return SACENV_E_SIZE;  // slot numbers: 31 bits
   if (!staged_range_ok(sp, g)) return SACENV_E_RANGE;
   return SACENV_OK;
@@ -1404,7 +1067,7 @@ int sacenv_replay_stage_draw_ctr(const SacenvReplayParams* p, const SacenvStaged
   hipLaunchKernelGGL(k_rb_draw_ctr, dim3((unsigned)((total + kPackTile - 1) / kPackTile)), dim3(kPackTile), 0,
                      (hipStream_t)stream, *p, geom(p, sp, g), seed, batch, n_batches, idx,
                      reinterpret_cast<unsigned long long*>(marks_prev), reinterpret_cast<unsigned long long*>(marks_cur),
-                     tiles, sp->offset == 0 ? 1 : 0);
+                     tiles, skip_owner(sp));
   return status();
 }
 
@@ -1467,38 +1130,28 @@ int sacenv_replay_stage_pack(const SacenvReplayParams* p, const SacenvStagedPara
   int rc = check_ctr_shape(p, sp, g, batch, n_batches);
   if (rc) return rc;
   if (!stage_cur || !stage_prev || !idx || !chunk || !tiles) return SACENV_E_NULL;
-  if (((reinterpret_cast<uintptr_t>(stage_cur) | reinterpret_cast<uintptr_t>(stage_prev)) & 15u) != 0u ||
-      (reinterpret_cast<uintptr_t>(chunk) & 3u) != 0u || cap < 0)
-    return SACENV_E_RANGE;
+  if (!stage_ptrs_ok(stage_cur, stage_prev, chunk) || cap < 0) return SACENV_E_RANGE;
   const int64_t total = (int64_t)batch * n_batches;
   if (total == 0) {  // no records: only the count
     const hipError_t e = hipMemsetAsync(chunk, 0, 4 * kChunkHdr, (hipStream_t)stream);
     return e == hipSuccess ? SACENV_OK : (int)e;
   }
-  StagedRows S;
-  S.cur = static_cast<const char*>(stage_cur);
-  S.prev = static_cast<const char*>(stage_prev);
-  for (int k = 0; k < SACENV_OBS_DIM; ++k) S.first[k] = sp->first_obs[k];
+  const StagedRows S = staged_rows(sp, stage_cur, stage_prev);
   const StagedGeom G = geom(p, sp, g);
-  const int skip_owner = sp->offset == 0 ? 1 : 0;
   const unsigned T = (unsigned)((total + kPackTile - 1) / kPackTile);
   if (!counted) {  // (the counter-based draw wrote the tile counts already)
     hipLaunchKernelGGL(k_rb_pack_count, dim3(T), dim3(kPackTile), 0, (hipStream_t)stream, *p, G, batch, n_batches,
-                       idx, skip_owner, tiles);
+                       idx, skip_owner(sp), tiles);
     if ((rc = status())) return rc;
   }
   hipLaunchKernelGGL(k_rb_pack_staged, dim3(T), dim3(kPackTile), 0, (hipStream_t)stream, *p, G, S, batch, n_batches,
-                     idx, static_cast<uint32_t*>(chunk), cap, skip_owner, tiles);
+                     idx, static_cast<uint32_t*>(chunk), cap, skip_owner(sp), tiles);
   return status();
 }
 
 int sacenv_replay_stage_unpack(int32_t world, int64_t chunk_bytes, int64_t cap, int32_t batch, int32_t n_batches,
                                const void* gathered, uint32_t* words, int32_t* status_word, void* stream) {
-  if (world < 1 || cap < 0 || batch < 0 || n_batches < 0) return SACENV_E_SIZE;
-  if ((int64_t)batch * n_batches >= ((int64_t)1 << 31) || (int64_t)world * cap >= ((int64_t)1 << 31))
-    return SACENV_E_SIZE;
-  if (chunk_bytes < 4 * (kChunkHdr + cap * kRecWords) || (chunk_bytes & 3) != 0) return SACENV_E_SIZE;
-  if ((int64_t)n_batches * words_per_batch(batch) >= ((int64_t)1 << 32)) return SACENV_E_SIZE;  // 32-bit offsets
+  if (!unpack_fits(world, chunk_bytes, cap, batch, n_batches)) return SACENV_E_SIZE;
   if (!gathered || !words || !status_word) return SACENV_E_NULL;
   const int64_t tiles = (cap + kPackTile - 1) / kPackTile;
   if (tiles == 0 || batch == 0) return SACENV_OK;
@@ -1521,7 +1174,7 @@ int sacenv_replay_stage_side(const SacenvReplayParams* p, const SacenvStagedPara
   a.p = *p;
   a.batch = batch;
   a.nb = n_batches;
-  a.skip_owner = sp->offset == 0 ? 1 : 0;
+  a.skip_owner = skip_owner(sp);
   if (draw) {
     if (!w->draw_idx || !w->marks_cur || !w->draw_tiles) return SACENV_E_NULL;
     a.Gd = geom(p, sp, w->draw_g);
@@ -1539,24 +1192,18 @@ int sacenv_replay_stage_side(const SacenvReplayParams* p, const SacenvStagedPara
   }
   if (pack) {
     if (!w->stage_cur || !w->stage_prev || !w->pack_idx || !w->pack_tiles || !w->chunk) return SACENV_E_NULL;
-    if (((reinterpret_cast<uintptr_t>(w->stage_cur) | reinterpret_cast<uintptr_t>(w->stage_prev)) & 15u) != 0u ||
-        (reinterpret_cast<uintptr_t>(w->chunk) & 3u) != 0u)
-      return SACENV_E_RANGE;
+    if (!stage_ptrs_ok(w->stage_cur, w->stage_prev, w->chunk)) return SACENV_E_RANGE;
     // the roles run side by side: the pack must not read what the draws write
     if (draw && (w->pack_idx == w->draw_idx || w->pack_tiles == w->draw_tiles)) return SACENV_E_RANGE;
     a.Gp = geom(p, sp, w->pack_g);
-    a.S.cur = static_cast<const char*>(w->stage_cur);
-    a.S.prev = static_cast<const char*>(w->stage_prev);
-    for (int k = 0; k < SACENV_OBS_DIM; ++k) a.S.first[k] = sp->first_obs[k];
+    a.S = staged_rows(sp, w->stage_cur, w->stage_prev);
     a.p_idx = w->pack_idx;
     a.p_tiles = w->pack_tiles;
     a.chunk = static_cast<uint32_t*>(w->chunk);
     a.n_pack = tiles;
   }
   if (unpack) {
-    if (w->world < 1) return SACENV_E_SIZE;
-    if (w->chunk_bytes < 4 * (kChunkHdr + w->cap * kRecWords) || (w->chunk_bytes & 3) != 0) return SACENV_E_SIZE;
-    if ((int64_t)n_batches * words_per_batch(batch) >= ((int64_t)1 << 32)) return SACENV_E_SIZE;  // 32-bit offsets
+    if (!unpack_fits(w->world, w->chunk_bytes, w->cap, batch, n_batches)) return SACENV_E_SIZE;
     if (!w->words || !w->status_word) return SACENV_E_NULL;
     // nor the unpack read the chunk the pack writes
     if (pack && static_cast<const char*>(w->gathered) < static_cast<const char*>(w->chunk) + w->chunk_bytes &&
@@ -1596,4 +1243,3 @@ int sacenv_copy_standin(const void* src, void* dst, int64_t bytes, int32_t workg
 }
 
 }  // extern "C"
-#endif  // SACENV_REPLAY_BODIES_ONLY

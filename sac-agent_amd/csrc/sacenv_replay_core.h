@@ -1,0 +1,382 @@
+// sacenv_replay_core.h — what the one-buffer unit (sacenv_replay.hip) and the population
+// unit (sacenv_replay_pop.hip) share: the constants, the arena layout, RB, the device
+// bodies of the five one-buffer kernels, the sharded and staged geometry, the MT19937
+// block twist, and the host rules both units apply (the parameter and call checks, the
+// store's and the gather's grid). No kernel and no entry point lives here: each unit
+// wraps the bodies in its own kernels.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sacenv.h"
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kMtN = SACENV_MT_N;
+constexpr int kMtM = 397;
+constexpr uint32_t kMtUpper = 0x80000000u;
+constexpr uint32_t kMtLower = 0x7fffffffu;
+constexpr uint32_t kMtMatrixA = 0x9908b0dfu;
+
+#include "mt19937.h"
+
+__host__ __device__ inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
+
+__host__ __device__ inline void replay_layout(const SacenvReplayParams& p, SacenvReplayLayout* o) {
+  const int64_t M = p.mem_size;
+  int64_t off = 0;
+  o->state = off;
+  off = align256(off + 4 * M * p.obs_dim);
+  o->new_state = off;
+  off = align256(off + 4 * M * p.obs_dim);
+  o->action = off;
+  off = align256(off + 4 * M * p.act_dim);
+  o->reward = off;
+  off = align256(off + 8 * M);
+  o->terminal = off;
+  off = align256(off + M);
+  o->mem_cntr = off;
+  off += 256;
+  o->mt_key = off;
+  off = align256(off + 4 * kMtN);
+  o->mt_pos = off;
+  off += 256;
+  o->total_bytes = off;
+}
+
+struct RB {
+  char* b;
+  SacenvReplayLayout L;
+  __device__ float* state() const { return reinterpret_cast<float*>(b + L.state); }
+  __device__ float* new_state() const { return reinterpret_cast<float*>(b + L.new_state); }
+  __device__ float* action() const { return reinterpret_cast<float*>(b + L.action); }
+  __device__ double* reward() const { return reinterpret_cast<double*>(b + L.reward); }
+  __device__ uint8_t* terminal() const { return reinterpret_cast<uint8_t*>(b + L.terminal); }
+  __device__ int64_t* cntr() const { return reinterpret_cast<int64_t*>(b + L.mem_cntr); }
+  __device__ uint32_t* key() const { return reinterpret_cast<uint32_t*>(b + L.mt_key); }
+  __device__ int32_t* pos() const { return reinterpret_cast<int32_t*>(b + L.mt_pos); }
+};
+
+// The bodies of the five one-buffer kernels are device functions: sacenv_replay.hip wraps
+// each in a kernel, and sacenv_replay_pop.hip runs them under a second grid dimension over
+// the members of a population. They index by blockIdx.x / gridDim.x only.
+__device__ __forceinline__ void init_body(const RB& r, uint32_t seed) {
+  if (threadIdx.x != 0) return;
+  uint32_t x = seed;  // init_genrand (numpy RandomState._legacy_seeding)
+  for (int i = 0; i < kMtN; ++i) {
+    r.key()[i] = x;
+    x = 1812433253u * (x ^ (x >> 30)) + (uint32_t)(i + 1);
+  }
+  *r.pos() = kMtN;
+  *r.cntr() = 0;
+}
+
+// store_transition for rows [0, n): row i -> (mem_cntr + i) % M. Rows that a
+// later row of the same call overwrites (i < n - M) are skipped, so the ring
+// ends exactly as n sequential calls leave it. Element-parallel over the
+// (n - first) x (D + A + 1) stored columns with 32-bit index math. mem_cntr
+// advances in a second launch (k_rb_advance), after every workgroup has read
+// it: stream order instead of a grid-wide atomic (one word takes ~90
+// returning atomics/µs) or an agent-scope acq_rel fence per workgroup. With the
+// count from the host (host_cntr >= 0) no workgroup reads it, so the first one
+// writes the advanced count and the second launch goes (one fixed launch cost,
+// ~5 us, per stored step).
+__device__ __forceinline__ void store_body(const SacenvReplayParams& p, const RB& r, int64_t host_cntr,
+                                           int64_t advance, int64_t n, int64_t offset,
+                                           const float* __restrict__ state, const float* __restrict__ action,
+                                           const void* __restrict__ reward, const float* __restrict__ new_state,
+                                           const float* __restrict__ final_state, const uint8_t* __restrict__ code,
+                                           uint8_t* __restrict__ last_term) {
+  const int64_t M = p.mem_size, c0 = (host_cntr >= 0 ? host_cntr : *r.cntr()) + offset;
+  if (host_cntr >= 0 && blockIdx.x == 0 && threadIdx.x == 0) *r.cntr() = host_cntr + advance;  // buffer.py:22
+  const int64_t first = n > M ? n - M : 0;
+  const uint32_t rows = (uint32_t)(n - first);
+  const uint32_t base = (uint32_t)((c0 + first) % M);  // ring row of stored row 0
+  const uint32_t D = (uint32_t)p.obs_dim, A = (uint32_t)p.act_dim, Mu = (uint32_t)M;
+  const uint32_t nD = rows * D, nA = rows * A, stored = nD + nA + rows;
+  // with last_term, rows a later row overwrites still update their env's byte
+  const uint32_t total = stored + (last_term != nullptr ? (uint32_t)first : 0u);
+  for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < total; q += gridDim.x * blockDim.x) {
+    if (q < nD) {
+      const uint32_t j = q / D, k = q - j * D;
+      uint32_t row = base + j;
+      row = row >= Mu ? row - Mu : row;
+      const int64_t src = (first + j) * (int64_t)D + k;
+      r.state()[(int64_t)row * D + k] = state[src];
+      const float* ns = (final_state != nullptr && code[first + j] != 0) ? final_state : new_state;
+      r.new_state()[(int64_t)row * D + k] = ns[src];
+    } else if (q < nD + nA) {
+      const uint32_t qq = q - nD, j = qq / A, k = qq - j * A;
+      uint32_t row = base + j;
+      row = row >= Mu ? row - Mu : row;
+      r.action()[(int64_t)row * A + k] = action[(first + j) * (int64_t)A + k];
+    } else if (q < stored) {
+      const uint32_t j = q - nD - nA;
+      uint32_t row = base + j;
+      row = row >= Mu ? row - Mu : row;
+      const int64_t i = first + j;
+      r.reward()[row] = p.reward_f32 ? (double)static_cast<const float*>(reward)[i]
+                                     : static_cast<const double*>(reward)[i];
+      uint32_t cd = code[i];
+      if (last_term != nullptr) {
+        // main.py:83 tests info['termination'], which only the termination
+        // chain writes (boat_env.py:84-105) and reset never clears (:120-126):
+        // codes 1..5 overwrite env i's last termination, others keep it
+        if (cd >= 1u && cd <= 5u) last_term[i] = (uint8_t)cd;
+        else cd = last_term[i];
+      }
+      r.terminal()[row] = (uint8_t)((p.terminal_mask >> (cd < 31 ? cd : 31)) & 1u);
+    } else {
+      const int64_t i = q - stored;  // a row the ring drops: only its env's byte
+      const uint32_t cd = code[i];
+      if (cd >= 1u && cd <= 5u) last_term[i] = (uint8_t)cd;
+    }
+  }
+}
+
+__device__ __forceinline__ void advance_body(const RB& r, int64_t n) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *r.cntr() += n;  // buffer.py:22
+}
+
+// np.random.choice(max_mem, batch) with replace=True, p=None: numpy legacy
+// randint(0, max_mem) -> masked rejection on 32-bit words (rng = max_mem-1;
+// rng == 0 draws nothing); words in order, accepted words fill the batch in
+// order, the stream stops after the batch-th accepted word: k_rb_draw_many below
+// (one 1 024-thread workgroup).
+
+// Sharded rows (sacenv_replay_sample_shard): ring row p holds the transition
+// with the latest global sequence number s <= mem_cntr - 1, s = p (mod M); this
+// shard wrote it iff (s mod period) is in [lo, hi). Rows of other shards come
+// out as zero bits.
+struct Shard {
+  int64_t period, lo, hi;  // period 0: every row is this shard's
+};
+__device__ __forceinline__ bool owns(const Shard& sh, int64_t cnt, int64_t M, int64_t row) {
+  if (sh.period == 0) return true;
+  const int64_t s = row + M * ((cnt - 1 - row) / M);
+  const int64_t u = s % sh.period;
+  return u >= sh.lo && u < sh.hi;
+}
+
+__device__ __forceinline__ void gather_body(const SacenvReplayParams& p, const RB& r, int batch,
+                                            const int64_t* __restrict__ idx, float* __restrict__ st,
+                                            float* __restrict__ ac, double* __restrict__ rw,
+                                            float* __restrict__ ns, uint8_t* __restrict__ tm, const Shard& sh) {
+  const int D = p.obs_dim, A = p.act_dim;
+  const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t nd = (int64_t)batch * D, na = (int64_t)batch * A;
+  const int64_t cnt = *r.cntr(), M = p.mem_size;
+  // (an index outside the ring -- a caller's, sacenv_replay_gather -- reads nothing: zero bits)
+  if (q < nd) {
+    const int64_t i = q / D, k = q - i * D, row = idx[i];
+    const bool own = row >= 0 && row < M && owns(sh, cnt, M, row);
+    if (st) st[q] = own ? r.state()[row * D + k] : 0.f;
+    if (ns) ns[q] = own ? r.new_state()[row * D + k] : 0.f;
+  } else if (q < nd + na) {
+    const int64_t qq = q - nd, i = qq / A, k = qq - i * A, row = idx[i];
+    if (ac) ac[qq] = row >= 0 && row < M && owns(sh, cnt, M, row) ? r.action()[row * A + k] : 0.f;
+  } else if (q < nd + na + batch) {
+    const int64_t i = q - nd - na, row = idx[i];
+    const bool own = row >= 0 && row < M && owns(sh, cnt, M, row);
+    if (rw) rw[i] = own ? r.reward()[row] : 0.0;
+    if (tm) tm[i] = own ? r.terminal()[row] : (uint8_t)0;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The staged sampler: the pooled buffer of main.py:78-90 -- every rank's envs
+// storing one transition each per step, one learn() (sample_buffer,
+// buffer.py:24-35) after every step -- sampled out of the rows the persistent
+// step launch wrote (sacenv_boat_segment's `stage`), with no ring. A ring of M
+// rows that takes `period` rows per step holds the last M sequence numbers;
+// with M <= seg * period every row learn k of segment g can reach (and the row
+// before it, for s) lies in segment g or g - 1, so two staged segments ARE the
+// ring. The index draws depend only on the sampling stream and the counts
+// stored, so segment g's are drawn before it steps, and the launch writes only
+// the rows some learn will read (sacenv_replay_stage_mark).
+
+struct StagedGeom {
+  int64_t period, offset, g;
+  int n, n_pad, seg, exp2;
+  double r_mem, r_period;  // 1 / mem_size, 1 / period (host IEEE divisions)
+};
+
+// floor(x / d) for 0 <= x < 2^52 and 0 < d < 2^31 from the rounded reciprocal rd:
+// the double estimate is off by at most one, fixed by one step each way (a 64-bit
+// integer division is a ~50-instruction sequence on the GPU)
+__device__ __forceinline__ int64_t div_floor(int64_t x, int64_t d, double rd) {
+  int64_t q = (int64_t)((double)x * rd);
+  q -= q * d > x ? 1 : 0;
+  q += (q + 1) * d <= x ? 1 : 0;
+  return q;
+}
+
+// The staged segment buffers are ENV-MAJOR (round 6): env e's 64-B row of step j of a
+// segment at (e x seg + j) x 64, its mark bits in the ceil(seg / 64) words from e x
+// that, bit j % 64 -- a row and its predecessor (the row before it: its s) share a
+// mark word (one atomic) and mostly a 128-B line.
+__device__ __forceinline__ int64_t stage_row(const StagedGeom& G, int e, int64_t j) {
+  return ((int64_t)e * G.seg + j) * 64;
+}
+__device__ __forceinline__ void mark_rows(unsigned long long* __restrict__ marks, const StagedGeom& G, int e,
+                                          int64_t j, unsigned long long bits) {
+  const int W = (G.seg + 63) / 64;
+  atomicOr(&marks[(int64_t)e * W + (j >> 6)], bits << (j & 63));
+}
+
+// ring row `row` at learn time (cntr rows stored) -> (global step q, global env u)
+__device__ __forceinline__ void resolve(int64_t row, int64_t cntr, int64_t M, const StagedGeom& G, int64_t* q,
+                                        int64_t* u) {
+  // the latest sequence number = row (mod M) below cntr
+  const int64_t s = row + M * div_floor(cntr - 1 - row, M, G.r_mem);
+  *q = div_floor(s, G.period, G.r_period);
+  *u = s - *q * G.period;
+}
+
+// n_batches consecutive np.random.choice(min(cntr_k, M), batch) calls on one
+// stream, cntr_k = cntr0 + (k + 1) * period (learn k follows step k's stores),
+// learns with cntr_k < batch skipped (continuous_agent.py:97-98: idx = -1, no
+// words). The general path (ranges that change between learns): one workgroup;
+// a whole 624-word block is tempered and tested at once (thread i: word i),
+// accepted words are ranked with a ballot per wave and a prefix over the
+// waves; a batch that completes inside the block ends at its last accepted
+// word, and the next batch re-tests the block from there.
+constexpr int kDrawThreads = 1024;
+__device__ __forceinline__ void mt_twist_block(const uint32_t* __restrict__ o, uint32_t* __restrict__ n, int tid) {
+  constexpr int kD = kMtN - kMtM;  // 227
+  if (tid < kD) n[tid] = mt_mix(o[tid], o[tid + 1], o[tid + kMtM]);
+  __syncthreads();
+  if (tid < kD) n[kD + tid] = mt_mix(o[kD + tid], o[kD + tid + 1], n[tid]);
+  __syncthreads();
+  if (tid < kMtN - 1 - 2 * kD) n[2 * kD + tid] = mt_mix(o[2 * kD + tid], o[2 * kD + tid + 1], n[kD + tid]);
+  __syncthreads();
+  if (tid == 0) n[kMtN - 1] = mt_mix(o[kMtN - 1], n[0], n[kMtM - 1]);
+  __syncthreads();
+}
+
+// kSample: one sample_buffer(batch) at the device count (sacenv_replay_sample: no
+// learn() skip below batch rows; graph-capturable like the store), else the nb
+// learns of a staged segment at counts cntr0 + (k + 1) * period.
+template <bool kSample>
+__device__ __forceinline__ void draw_many_body(const SacenvReplayParams& p, const RB& r, int batch, int nb,
+                                               int64_t cntr0, int64_t period, int64_t* __restrict__ idx) {
+  __shared__ uint32_t blk[2][kMtN];
+  __shared__ int wcnt[kDrawThreads / kWave];
+  __shared__ int s_end;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  constexpr int kWaves = kDrawThreads / kWave;
+  int cur = 0, pos = *r.pos();
+  if (pos < 0) {  // a poisoned stream (a staged draw ran short): draw nothing, keep the poison
+    for (int64_t i = tid; i < (int64_t)nb * batch; i += kDrawThreads) idx[i] = -1;
+    return;
+  }
+  for (int i = tid; i < kMtN; i += kDrawThreads) blk[0][i] = r.key()[i];
+  bool advanced = false;
+  __syncthreads();
+  int k = 0, filled = 0;
+  while (k < nb) {
+    const int64_t c = kSample ? *r.cntr() : cntr0 + (int64_t)(k + 1) * period;
+    const int64_t max_mem = c < p.mem_size ? c : p.mem_size;
+    const uint32_t rng = (uint32_t)(max_mem - 1);
+    const bool skip = !kSample && c < batch;
+    if (skip || rng == 0u) {  // learn() returns before sampling, or numpy's off + 0: no words
+      for (int i = tid; i < batch; i += kDrawThreads) idx[(int64_t)k * batch + i] = skip ? -1 : 0;
+      ++k;
+      continue;
+    }
+    uint32_t mask = rng;
+    mask |= mask >> 1;
+    mask |= mask >> 2;
+    mask |= mask >> 4;
+    mask |= mask >> 8;
+    mask |= mask >> 16;
+    if (pos >= kMtN) {
+      mt_twist_block(blk[cur], blk[cur ^ 1], tid);
+      cur ^= 1;
+      pos = 0;
+      advanced = true;
+    }
+    const bool valid = tid >= pos && tid < kMtN;
+    const uint32_t w = valid ? (mt_temper(blk[cur][tid]) & mask) : 0u;
+    const bool acc = valid && w <= rng;
+    const unsigned long long bal = __ballot(acc);
+    if (lane == 0) wcnt[wv] = __popcll(bal);
+    __syncthreads();
+    int excl = 0, total = 0;
+#pragma unroll
+    for (int q = 0; q < kWaves; ++q) {
+      const int v = wcnt[q];
+      excl += q < wv ? v : 0;
+      total += v;
+    }
+    const int rank = excl + __popcll(bal & ((1ull << lane) - 1ull));
+    const int take = batch - filled;
+    if (acc && rank < take) idx[(int64_t)k * batch + filled + rank] = (int64_t)w;
+    if (total >= take) {  // the take-th accepted word ends batch k
+      if (acc && rank == take - 1) s_end = tid;
+      __syncthreads();
+      pos = s_end + 1;
+      ++k;
+      filled = 0;
+    } else {
+      filled += total;
+      pos = kMtN;
+    }
+    __syncthreads();  // wcnt / s_end are rewritten by the next round
+  }
+  if (advanced)
+    for (int i = tid; i < kMtN; i += kDrawThreads) r.key()[i] = blk[cur][i];
+  if (tid == 0) *r.pos() = pos;
+}
+
+int check_replay(const SacenvReplayParams* p) {
+  if (p == nullptr) return SACENV_E_NULL;
+  if (p->mem_size <= 0 || p->mem_size > 0x7FFFFFFFLL || p->obs_dim <= 0 || p->act_dim <= 0)
+    return SACENV_E_SIZE;  // 32-bit ring rows; randint on 32-bit words
+  return SACENV_OK;
+}
+
+// The store's grid for n rows per buffer: the min(n, M) rows the ring keeps x (D + A + 1)
+// columns, and with last_term one element per row it drops; at most 8192 blocks of 256
+// (store_body strides).
+inline int store_grid(const SacenvReplayParams* p, int64_t n, const uint8_t* last_term, int64_t* blocks) {
+  const int64_t rows = n > p->mem_size ? p->mem_size : n;
+  const int64_t total = rows * ((int64_t)p->obs_dim + p->act_dim + 1) + (last_term ? n - rows : 0);
+  if (total >= (1LL << 32)) return SACENV_E_SIZE;  // 32-bit element index per buffer and call
+  *blocks = (total + 255) / 256;
+  if (*blocks > 8192) *blocks = 8192;
+  return SACENV_OK;
+}
+
+// a buffer's elements of one sample or gather, and the gather's grid.x: one thread each
+inline int64_t batch_elems(const SacenvReplayParams* p, int32_t batch) {
+  return (int64_t)batch * ((int64_t)p->obs_dim + p->act_dim + 1);
+}
+inline unsigned gather_blocks(const SacenvReplayParams* p, int32_t batch) {
+  return (unsigned)((batch_elems(p, batch) + 255) / 256);
+}
+
+// the argument rules of the sample / gather family, after the parameters' (a gather has no
+// `stored`)
+inline int check_batch_call(const void* arena, const int64_t* idx, int32_t batch, int64_t stored = 1) {
+  if (batch < 0) return SACENV_E_SIZE;
+  if (stored <= 0) return SACENV_E_SIZE;  // np.random.choice(0, n) raises
+  if (arena == nullptr || idx == nullptr) return SACENV_E_NULL;
+  return SACENV_OK;
+}
+
+RB make_rb(const SacenvReplayParams& p, void* arena) {
+  RB r;
+  r.b = static_cast<char*>(arena);
+  replay_layout(p, &r.L);
+  return r;
+}
+
+int status() {
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? SACENV_OK : (int)err;
+}
+
+}  // namespace

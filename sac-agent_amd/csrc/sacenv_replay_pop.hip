@@ -12,13 +12,12 @@
 // per-member table, the seeds of the init launch, is read from the kernel arguments
 // with scalar loads at an SGPR offset, as PopArgs is in sacenv_sac_pop.hip.
 //
-// This is a translation unit of its own, which includes sacenv_replay.hip for the
-// device bodies and the host helpers: the one-buffer kernels, and above all the
-// staged, side and stand-in kernels of the timed replay path, are compiled where
-// they were, alone (tools/kernel_diff.py; DESIGN.md §4.6.1 has the result and the
+// This is a translation unit of its own, which shares the device bodies and the host
+// rules with sacenv_replay.hip through sacenv_replay_core.h: the one-buffer kernels, and
+// above all the staged, side and stand-in kernels of the timed replay path, are compiled
+// where they were, alone (tools/kernel_diff.py; DESIGN.md §4.6.1 has the result and the
 // resource table).
-#define SACENV_REPLAY_BODIES_ONLY
-#include "sacenv_replay.hip"
+#include "sacenv_replay_core.h"
 
 #include "sacenv_population_replay.h"
 
@@ -92,16 +91,20 @@ bool aligned256(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 25
 
 int gather_pop(const SacenvReplayParams* p, int32_t members, const RB& r, int32_t batch, const int64_t* idx,
                float* state, float* action, double* reward, float* new_state, uint8_t* terminal, void* stream) {
-  const int64_t total = (int64_t)batch * (p->obs_dim + p->act_dim + 1);
-  hipLaunchKernelGGL(k_rb_gather_pop, dim3((unsigned)((total + 255) / 256), members), dim3(256), 0,
-                     (hipStream_t)stream, *p, r, r.L.total_bytes, batch, idx, state, action, reward, new_state,
-                     terminal);
+  hipLaunchKernelGGL(k_rb_gather_pop, dim3(gather_blocks(p, batch), members), dim3(256), 0, (hipStream_t)stream, *p,
+                     r, r.L.total_bytes, batch, idx, state, action, reward, new_state, terminal);
   return status();
 }
 
-// a member's elements of one sample or gather: the gather's grid.x is their count / 256
-bool batch_fits(const SacenvReplayParams* p, int32_t batch) {
-  return (int64_t)batch * ((int64_t)p->obs_dim + p->act_dim + 1) < (1LL << 32);
+// the rules of a population sample / gather: the one-buffer call's, the arena's alignment (a
+// member's arena starts member_bytes, a multiple of 256, after the last) and a 32-bit count of
+// a member's elements (the gather's grid.x is that count / 256)
+int check_pop_batch_call(const SacenvReplayParams* p, int32_t members, const void* arena, const int64_t* idx,
+                         int32_t batch, int64_t stored = 1) {
+  int rc = rb_pop_check(p, members);
+  if (rc || (rc = check_batch_call(arena, idx, batch, stored))) return rc;
+  if (!aligned256(arena) || batch_elems(p, batch) >= (1LL << 32)) return SACENV_E_SIZE;
+  return SACENV_OK;
 }
 
 }  // namespace
@@ -147,16 +150,13 @@ extern "C" int sacenv_replay_pop_store(const SacenvReplayParams* p, int32_t memb
   if (n == 0) return SACENV_OK;
   if (!arena || !state || !action || !reward || !new_state || !code) return SACENV_E_NULL;
   if (!aligned256(arena)) return SACENV_E_SIZE;
-  const int64_t rows = n > p->mem_size ? p->mem_size : n;
-  const int64_t total = rows * ((int64_t)p->obs_dim + p->act_dim + 1) + (last_term ? n - rows : 0);
-  if (total >= (1LL << 32)) return SACENV_E_SIZE;  // 32-bit element index per member and call
+  int64_t blocks;
+  if ((rc = store_grid(p, n, last_term, &blocks))) return rc;
   if (members == 1)
     return cntr >= 0 ? sacenv_replay_store_env_at(p, arena, cntr, n, state, action, reward, new_state, final_state,
                                                   code, last_term, stream)
                      : sacenv_replay_store_env(p, arena, n, state, action, reward, new_state, final_state, code,
                                                last_term, stream);
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
   const RB r = make_rb(*p, arena);
   hipLaunchKernelGGL(k_rb_store_pop, dim3((unsigned)blocks, members), dim3(256), 0, (hipStream_t)stream, *p, r,
                      r.L.total_bytes, cntr, n, n, state, action, reward, new_state, final_state, code, last_term);
@@ -169,12 +169,8 @@ extern "C" int sacenv_replay_pop_store(const SacenvReplayParams* p, int32_t memb
 extern "C" int sacenv_replay_pop_sample(const SacenvReplayParams* p, int32_t members, void* arena, int32_t batch,
                                         int64_t stored, int64_t* idx, float* state, float* action, double* reward,
                                         float* new_state, uint8_t* terminal, void* stream) {
-  int rc = rb_pop_check(p, members);
+  int rc = check_pop_batch_call(p, members, arena, idx, batch, stored);
   if (rc) return rc;
-  if (batch < 0) return SACENV_E_SIZE;
-  if (stored <= 0) return SACENV_E_SIZE;  // np.random.choice(0, n) raises
-  if (arena == nullptr || idx == nullptr) return SACENV_E_NULL;
-  if (!aligned256(arena) || !batch_fits(p, batch)) return SACENV_E_SIZE;
   if (batch == 0) return SACENV_OK;
   if (members == 1)
     return sacenv_replay_sample(p, arena, batch, stored, idx, state, action, reward, new_state, terminal, stream);
@@ -188,11 +184,8 @@ extern "C" int sacenv_replay_pop_sample(const SacenvReplayParams* p, int32_t mem
 extern "C" int sacenv_replay_pop_gather(const SacenvReplayParams* p, int32_t members, void* arena, int32_t batch,
                                         const int64_t* idx, float* state, float* action, double* reward,
                                         float* new_state, uint8_t* terminal, void* stream) {
-  const int rc = rb_pop_check(p, members);
+  const int rc = check_pop_batch_call(p, members, arena, idx, batch);
   if (rc) return rc;
-  if (batch < 0) return SACENV_E_SIZE;
-  if (arena == nullptr || idx == nullptr) return SACENV_E_NULL;
-  if (!aligned256(arena) || !batch_fits(p, batch)) return SACENV_E_SIZE;
   if (batch == 0) return SACENV_OK;
   if (members == 1)
     return sacenv_replay_gather(p, arena, batch, idx, state, action, reward, new_state, terminal, stream);

@@ -7,10 +7,10 @@
 // shared layout and Adam scalars) with every pointer moved by m member strides
 // and the six per-member scalars taken from a table in the kernel arguments.
 //
-// This is a translation unit of its own, which includes sacenv_sac.hip for the
-// device bodies and the host helpers: compiled in one unit, a second caller of
-// the bodies changes how the compiler schedules the one-agent kernels
-// (tools/kernel_diff.py), and those stay as they are.
+// This is a translation unit of its own, which shares the device bodies and the
+// host helpers with sacenv_sac.hip through sacenv_sac_core.h: compiled in one
+// unit, a second caller of the bodies changes how the compiler schedules the
+// one-agent kernels (tools/kernel_diff.py), and those stay as they are.
 //
 // rows_body and update_body index SacArgs' arrays by role and net, which are
 // run-time values: a by-value copy of the member's SacArgs with such an index on
@@ -20,9 +20,8 @@
 // that everything below the body is inlined, hence the always_inline pushed over
 // the include (one agent's kernels inline all of it too). The update kernel keeps
 // the member's SacArgs in LDS. DESIGN.md §4.8 has the resource table.
-#define SACENV_SAC_BODIES_ONLY
 #pragma clang attribute push(__attribute__((always_inline)), apply_to = function)
-#include "sacenv_sac.hip"
+#include "sacenv_sac_core.h"
 #pragma clang attribute pop
 
 namespace {

@@ -17,9 +17,8 @@ INCLUDE = os.path.join(REPO_ROOT, "include")
 BUILD = os.path.join(PKG_ROOT, "build")
 LIB = os.path.join(BUILD, "libsacenv.so")
 SOURCES = ("sacenv_boat.hip", "sacenv_replay.hip", "sacenv_sac.hip", "sacenv_episodes.hip",
-           "sacenv_sac_pop.hip",       # (includes sacenv_sac.hip for its device bodies)
-           "sacenv_replay_pop.hip")    # (includes sacenv_replay.hip for its device bodies)
-HEADERS = ("mt19937.h",)
+           "sacenv_sac_pop.hip", "sacenv_replay_pop.hip")
+HEADERS = ("mt19937.h", "sacenv_replay_core.h", "sacenv_sac_core.h")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fPIC", "-shared", "-Wall")
 

@@ -300,27 +300,24 @@ def load(path: str | None = None):
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
         f.restype, f.argtypes = res, args
-    ES = C.POINTER(EpisodeScan)
-    for name, args in zip(EPISODE_EXPORTS, ([ES, C.POINTER(_i64)], [ES, _p, _p, _p, _p, _i64, _p])):
-        f = getattr(lib, name, None)   # absent from a library built before sacenv_episodes.h
-        if f is not None:
-            f.restype, f.argtypes = C.c_int, args
-    QP = C.POINTER(SacParams)
-    for name, args in zip(POPULATION_EXPORTS, (
+    ES, QP = C.POINTER(EpisodeScan), C.POINTER(SacParams)
+    optional = (   # the headers beside sacenv.h: (names, argtypes), absent from a library built before them
+        (EPISODE_EXPORTS, ([ES, C.POINTER(_i64)], [ES, _p, _p, _p, _p, _i64, _p])),
+        (POPULATION_EXPORTS, (
             [QP, _i32, C.POINTER(SacPopLayout)], [QP, _i32, _p, _p],
             [QP, _i32, _p, _p, _i32, _p, _p, _p, _p],
-            [QP, _i32, C.POINTER(SacMember), _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p])):
-        f = getattr(lib, name, None)   # absent from a library built before sacenv_population.h
-        if f is not None:
-            f.restype, f.argtypes = C.c_int, args
-    for name, args in zip(REPLAY_POP_EXPORTS, (
+            [QP, _i32, C.POINTER(SacMember), _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p])),
+        (REPLAY_POP_EXPORTS, (
             [RP, _i32, C.POINTER(ReplayPopLayout)], [RP, _i32, _p, C.POINTER(C.c_uint32), _p],
             [RP, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
             [RP, _i32, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p],
-            [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])):
-        f = getattr(lib, name, None)   # absent from a library built before sacenv_population_replay.h
-        if f is not None:
-            f.restype, f.argtypes = C.c_int, args
+            [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])))
+    for names, argtypes in optional:
+        assert len(names) == len(argtypes)
+        for name, args in zip(names, argtypes):
+            f = getattr(lib, name, None)
+            if f is not None:
+                f.restype, f.argtypes = C.c_int, args
     v = lib.sacenv_abi_version()
     if v != ABI_VERSION:
         raise SacenvError(f"libsacenv ABI {v} != expected {ABI_VERSION}")

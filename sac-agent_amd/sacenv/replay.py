@@ -30,31 +30,47 @@ from . import _lib
 TERMINAL_GOAL = 1 << 1   # terminal = (code == 1): env term reached_goal, or a 0/1 done array
 
 
-class DeviceReplayBuffer:
-    def __init__(self, max_size: int, input_shape, n_actions: int, *, device=None, seed: int = 0,
-                 reward_f32: bool = True, terminal_mask: int = TERMINAL_GOAL):
+def _cuda_device(device, who: str) -> torch.device:
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who} runs on a GPU (HIP); no CPU path")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _replay_params(mem_size: int, obs_dim: int, act_dim: int, reward_f32=True,
+                   terminal_mask: int = TERMINAL_GOAL) -> _lib.ReplayParams:
+    p = _lib.ReplayParams()
+    p.mem_size, p.obs_dim, p.act_dim = int(mem_size), int(obs_dim), int(act_dim)
+    p.reward_f32, p.terminal_mask = int(bool(reward_f32)), int(terminal_mask)
+    return p
+
+
+class _ReplayArena:
+    """What ``DeviceReplayBuffer`` and ``PopulationReplay`` share: ``lead`` buffers -- ``()``: the
+    one buffer, ``(P,)``: a population's -- each laid out by ``sacenv_replay_layout``, as the rows
+    of one ``[*lead, total_bytes]`` arena. Every field view, store input and sampled output has
+    ``lead`` in front of the one buffer's shape."""
+
+    def __init__(self, lead: tuple, max_size: int, input_shape, n_actions: int, device, reward_f32, terminal_mask):
         self.lib = _lib.load()
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("DeviceReplayBuffer runs on a GPU (HIP); no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device(device, type(self).__name__)
+        self.lead, self._k, self._buffers = lead, len(lead), int(np.prod(lead))   # lead: () or (P,)
         shape = (int(input_shape),) if np.isscalar(input_shape) else tuple(int(d) for d in input_shape)
         self.input_shape = shape
         self.mem_size = int(max_size)
         self.n_actions = int(n_actions)
-        p = _lib.ReplayParams()
-        p.mem_size, p.obs_dim, p.act_dim = self.mem_size, int(np.prod(shape)), self.n_actions
-        p.reward_f32, p.terminal_mask = int(bool(reward_f32)), int(terminal_mask)
-        self.params = p
+        self.params = p = _replay_params(self.mem_size, int(np.prod(shape)), self.n_actions, reward_f32,
+                                         terminal_mask)
         self._pp = C.byref(p)
+        # (read per store: a ctypes field costs more than an attribute)
+        self._obs_dim, self._reward_dtype = p.obs_dim, torch.float32 if p.reward_f32 else torch.float64
         self.layout = L = _lib.replay_layout(p)
-        self.arena = torch.zeros(int(L.total_bytes), dtype=torch.uint8, device=self.device)
-        M, D, A = self.mem_size, p.obs_dim, self.n_actions
+        self.arena = torch.zeros((*lead, int(L.total_bytes)), dtype=torch.uint8, device=self.device)
+        M, A = self.mem_size, self.n_actions
 
-        def view(off, dtype, *shp):
+        def view(off, dtype, *shp):   # [*lead, *shp]: the field of every buffer, strided over the arena's rows
             esz = torch.empty((), dtype=dtype).element_size()
-            return self.arena[off: off + int(np.prod(shp)) * esz].view(dtype).view(*shp)
+            return self.arena[..., off: off + int(np.prod(shp)) * esz].view(dtype).unflatten(-1, shp)
 
         self.state_memory = view(L.state, torch.float32, M, *shape)
         self.new_state_memory = view(L.new_state, torch.float32, M, *shape)
@@ -64,20 +80,78 @@ class DeviceReplayBuffer:
         self._cntr = view(L.mem_cntr, torch.int64, 1)
         self.mt_key = view(L.mt_key, torch.int32, _lib.MT_N)
         self.mt_pos = view(L.mt_pos, torch.int32, 1)
-        self.mem_cntr = 0                        # host mirror (buffer.py:6)
+        self.mem_cntr = 0                        # host mirror (buffer.py:6): every buffer's count
         # env -> u8 [num_envs] info['termination'] codes; weak keys: an env that is
         # garbage-collected takes its bytes with it (no id() reuse by a new env)
         self._last_term = weakref.WeakKeyDictionary()
-        _lib.check(self.lib.sacenv_replay_init(self._pp, self.arena.data_ptr(), int(seed) & 0xFFFFFFFF,
-                                               self.stream))
 
     @property
     def stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def _dev(self, x, dtype):
+        if type(x) is torch.Tensor and x.dtype == dtype and x.device == self.device:
+            return x.contiguous()     # (already in place: torch.as_tensor alone costs 0.3 us more per input)
         t = torch.as_tensor(x, device=self.device)
         return t.to(dtype).contiguous() if t.dtype != dtype else t.contiguous()
+
+    def _env_last_term(self, env):
+        """The env's persistent byte per env (``store_env_step`` with ``reference_terminal``)."""
+        last = self._last_term.get(env)
+        if last is None or last.numel() != env.num_envs:
+            last = torch.zeros(env.num_envs, dtype=torch.uint8, device=self.device)
+            self._last_term[env] = last
+        return last
+
+    def _store_inputs(self, state, action, reward, new_state, code, final_state, last_term):
+        """The inputs of a store, checked: n (rows per buffer) and the pointers of state, action,
+        reward, new_state, final_state, code and last_term, in the order every store entry point
+        takes them. The first six are made contiguous device tensors of the kernels' types (kept
+        alive in ``_keep``), ``last_term`` is taken as given. Every tensor holds ``[*lead, n]``
+        rows, so buffer m's rows are its m-th block of n."""
+        k, P = self._k, self._buffers
+        s = self._dev(state, torch.float32)
+        shape = s.shape
+        if len(shape) <= k or (k and shape[0] != P):
+            raise ValueError(f"state must be [{', '.join(map(str, (*self.lead, 'n', '...')))}] (one block of rows "
+                             f"per buffer), got {list(shape)}")
+        n = shape[k]
+        a = self._dev(action, torch.float32)
+        r = self._dev(reward, self._reward_dtype)
+        ns = self._dev(new_state, torch.float32)
+        c = self._dev(code, torch.uint8)
+        fs = None if final_state is None else self._dev(final_state, torch.float32)
+        rows = n * P
+        if (s.numel() != rows * self._obs_dim or ns.shape != shape or a.numel() != rows * self.n_actions
+                or r.numel() != rows or c.numel() != rows or (fs is not None and fs.shape != shape)
+                or (n and k and not (a.dim() and r.dim() and c.dim() and a.shape[0] == r.shape[0] == c.shape[0] == P))):
+            raise ValueError(f"transition shapes do not match the buffer{' and its members' if k else ''}")
+        lt = last_term
+        if lt is not None and (not isinstance(lt, torch.Tensor) or lt.dtype != torch.uint8 or lt.device != self.device
+                               or lt.numel() != rows or not lt.is_contiguous()):
+            raise ValueError("last_term must be a contiguous u8 device tensor with one byte per row")
+        self._keep = (s, a, r, ns, c, fs)
+        return n, (s.data_ptr(), a.data_ptr(), r.data_ptr(), ns.data_ptr(), None if fs is None else fs.data_ptr(),
+                   c.data_ptr(), None if lt is None else lt.data_ptr())
+
+    def _outputs(self, B: int, idx: bool = False):
+        """(st, ac, rw, ns, tm, idx) of one sample or gather: ``[*lead, B, ...]``, unwritten. (The
+        sizes as arguments: torch parses them faster than a tuple, 0.6 us per tensor.)"""
+        lead, dev = self.lead, self.device
+        st = torch.empty(*lead, B, *self.input_shape, dtype=torch.float32, device=dev)
+        ns = torch.empty_like(st)
+        ac = torch.empty(*lead, B, self.n_actions, dtype=torch.float32, device=dev)
+        rw = torch.empty(*lead, B, dtype=torch.float64, device=dev)
+        tm = torch.empty(*lead, B, dtype=torch.uint8, device=dev)
+        return st, ac, rw, ns, tm, (torch.empty(*lead, B, dtype=torch.int64, device=dev) if idx else None)
+
+
+class DeviceReplayBuffer(_ReplayArena):
+    def __init__(self, max_size: int, input_shape, n_actions: int, *, device=None, seed: int = 0,
+                 reward_f32: bool = True, terminal_mask: int = TERMINAL_GOAL):
+        super().__init__((), max_size, input_shape, n_actions, device, reward_f32, terminal_mask)
+        _lib.check(self.lib.sacenv_replay_init(self._pp, self.arena.data_ptr(), int(seed) & 0xFFFFFFFF,
+                                               self.stream))
 
     def store_batch(self, state, action, reward, new_state, code, final_state=None,
                     last_term=None, graph_safe: bool = False) -> None:
@@ -89,32 +163,12 @@ class DeviceReplayBuffer:
         count goes into the launch (one launch, ``sacenv_replay_store_env_at``), which a
         captured graph would freeze; ``graph_safe=True`` reads and advances the device
         count instead (``sacenv_replay_store_env``: a store and an advance launch)."""
-        s = self._dev(state, torch.float32)
-        n = s.shape[0]
-        a = self._dev(action, torch.float32).reshape(n, -1)
-        r = self._dev(reward, torch.float32 if self.params.reward_f32 else torch.float64).reshape(n)
-        ns = self._dev(new_state, torch.float32)
-        c = self._dev(code, torch.uint8).reshape(n)
-        fs = None if final_state is None else self._dev(final_state, torch.float32)
-        if a.shape[1] != self.n_actions or s.shape != ns.shape:
-            raise ValueError("transition shapes do not match the buffer")
-        lt = None
-        if last_term is not None:
-            lt = last_term
-            if (lt.dtype != torch.uint8 or lt.device != self.device or lt.numel() != n
-                    or not lt.is_contiguous()):
-                raise ValueError("last_term must be a contiguous u8 device tensor with one byte per row")
+        n, ptrs = self._store_inputs(state, action, reward, new_state, code, final_state, last_term)
         if graph_safe:  # the device count, read and advanced on the device
-            _lib.check(self.lib.sacenv_replay_store_env(
-                self._pp, self.arena.data_ptr(), n, s.data_ptr(), a.data_ptr(), r.data_ptr(), ns.data_ptr(),
-                None if fs is None else fs.data_ptr(), c.data_ptr(), None if lt is None else lt.data_ptr(),
-                self.stream))
+            _lib.check(self.lib.sacenv_replay_store_env(self._pp, self.arena.data_ptr(), n, *ptrs, self.stream))
         else:  # the host issues every store, so it knows the count: one launch (sacenv.h)
-            _lib.check(self.lib.sacenv_replay_store_env_at(
-                self._pp, self.arena.data_ptr(), self.mem_cntr, n, s.data_ptr(), a.data_ptr(), r.data_ptr(),
-                ns.data_ptr(), None if fs is None else fs.data_ptr(), c.data_ptr(),
-                None if lt is None else lt.data_ptr(), self.stream))
-        self._keep = (s, a, r, ns, c, fs)
+            _lib.check(self.lib.sacenv_replay_store_env_at(self._pp, self.arena.data_ptr(), self.mem_cntr, n, *ptrs,
+                                                           self.stream))
         self.mem_cntr += n
 
     def store_env_step(self, prev_obs, actions, env, reference_terminal: bool = True) -> None:
@@ -128,14 +182,8 @@ class DeviceReplayBuffer:
         episode every transition is stored terminal until another ending
         overwrites it. The buffer keeps that byte per env. ``False``: terminal
         only on the step that reached the goal (the evident intent)."""
-        last = None
-        if reference_terminal:
-            last = self._last_term.get(env)
-            if last is None or last.numel() != env.num_envs:
-                last = torch.zeros(env.num_envs, dtype=torch.uint8, device=self.device)
-                self._last_term[env] = last
         self.store_batch(prev_obs, actions, env.reward, env.obs, env.term, final_state=env.final_obs,
-                         last_term=last)
+                         last_term=self._env_last_term(env) if reference_terminal else None)
 
     def sample(self, batch_size: int, as_bool: bool = True):
         """sample_buffer (buffer.py:24-35) on device: (states, actions, rewards, states_, dones, idx).
@@ -144,12 +192,7 @@ class DeviceReplayBuffer:
         B = int(batch_size)
         if self.mem_cntr == 0 and B > 0:
             raise ValueError("a must be greater than 0 unless no samples are taken")
-        idx = torch.empty(B, dtype=torch.int64, device=self.device)
-        st = torch.empty((B, *self.input_shape), dtype=torch.float32, device=self.device)
-        ns = torch.empty_like(st)
-        ac = torch.empty((B, self.n_actions), dtype=torch.float32, device=self.device)
-        rw = torch.empty(B, dtype=torch.float64, device=self.device)
-        tm = torch.empty(B, dtype=torch.uint8, device=self.device)
+        st, ac, rw, ns, tm, idx = self._outputs(B, idx=True)
         _lib.check(self.lib.sacenv_replay_sample(
             self._pp, self.arena.data_ptr(), B, self.mem_cntr, idx.data_ptr(), st.data_ptr(),
             ac.data_ptr(), rw.data_ptr(), ns.data_ptr(), tm.data_ptr(), self.stream))
@@ -161,11 +204,7 @@ class DeviceReplayBuffer:
         zeros (``sacenv_replay_gather``)."""
         idx = idx.to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
         B = idx.numel()
-        st = torch.empty((B, *self.input_shape), dtype=torch.float32, device=self.device)
-        ns = torch.empty_like(st)
-        ac = torch.empty((B, self.n_actions), dtype=torch.float32, device=self.device)
-        rw = torch.empty(B, dtype=torch.float64, device=self.device)
-        tm = torch.empty(B, dtype=torch.uint8, device=self.device)
+        st, ac, rw, ns, tm, _ = self._outputs(B)
         _lib.check(self.lib.sacenv_replay_gather(
             self._pp, self.arena.data_ptr(), B, idx.data_ptr(), st.data_ptr(), ac.data_ptr(), rw.data_ptr(),
             ns.data_ptr(), tm.data_ptr(), self.stream))
@@ -196,20 +235,11 @@ class ShardedReplayBuffer(DeviceReplayBuffer):
 
     def store_batch(self, state, action, reward, new_state, code, final_state=None, last_term=None) -> None:
         """This rank's n rows of one pooled step (rank-local inputs, as DeviceReplayBuffer)."""
-        s = self._dev(state, torch.float32)
-        n = s.shape[0]
+        n, ptrs = self._store_inputs(state, action, reward, new_state, code, final_state, last_term)
         if n != self.n:
             raise ValueError(f"a step stores this rank's {self.n} rows")
-        a = self._dev(action, torch.float32).reshape(n, -1)
-        r = self._dev(reward, torch.float32 if self.params.reward_f32 else torch.float64).reshape(n)
-        ns = self._dev(new_state, torch.float32)
-        c = self._dev(code, torch.uint8).reshape(n)
-        fs = None if final_state is None else self._dev(final_state, torch.float32)
-        _lib.check(self.lib.sacenv_replay_store_shard(
-            self._pp, self.arena.data_ptr(), n, self.offset, self.period, s.data_ptr(), a.data_ptr(),
-            r.data_ptr(), ns.data_ptr(), None if fs is None else fs.data_ptr(), c.data_ptr(),
-            None if last_term is None else last_term.data_ptr(), self.stream))
-        self._keep = (s, a, r, ns, c, fs)
+        _lib.check(self.lib.sacenv_replay_store_shard(self._pp, self.arena.data_ptr(), n, self.offset, self.period,
+                                                      *ptrs, self.stream))
         self.mem_cntr += self.period
 
     def sample(self, batch_size: int, as_bool: bool = True):
@@ -318,11 +348,7 @@ class StagedReplay:
                  device=None, group=None, terminal_mask: int = TERMINAL_GOAL, sampler: str = "mt",
                  exchange: str = "allreduce", standin: dict | None = None):
         self.lib = _lib.load()
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("StagedReplay runs on a GPU (HIP); no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device(device, "StagedReplay")
         if sampler not in ("mt", "philox") or exchange not in ("allreduce", "allgather"):
             raise ValueError("sampler is 'mt' or 'philox'; exchange is 'allreduce' or 'allgather'")
         self.sampler, self.exchange = sampler, exchange
@@ -360,11 +386,8 @@ class StagedReplay:
             self._pp = self._rb._pp
         else:  # (no stream: only the buffer's shape)
             self._rb = None
-            p = _lib.ReplayParams()
-            p.mem_size, p.obs_dim, p.act_dim = self.mem_size, _lib.OBS_DIM, 1
-            p.reward_f32, p.terminal_mask = 1, int(terminal_mask)
-            self._params = p
-            self._pp = C.byref(p)
+            self._params = _replay_params(self.mem_size, _lib.OBS_DIM, 1, True, terminal_mask)
+            self._pp = C.byref(self._params)
         self._status = torch.zeros(4, dtype=torch.int32, device=self.device)
         nb = self.N_BUFFERS
         self.stage = [torch.zeros(self.seg * self.n_pad * 64, dtype=torch.uint8, device=self.device)
@@ -620,8 +643,7 @@ def staged_chunk(n: int, n_pad: int, world: int, mem_size: int, batch: int, seg:
     """(records, bytes) of one rank's all-gather chunk for this shape
     (``sacenv_replay_stage_chunk``): the same on every rank."""
     lib = _lib.load()
-    p = _lib.ReplayParams()
-    p.mem_size, p.obs_dim, p.act_dim, p.reward_f32, p.terminal_mask = int(mem_size), _lib.OBS_DIM, 1, 1, 2
+    p = _replay_params(mem_size, _lib.OBS_DIM, 1)
     sp = _lib.StagedParams()
     sp.period, sp.offset, sp.n, sp.n_pad, sp.seg, sp.experiment = world * n, 0, n, n_pad, seg, experiment
     cap, nbytes = C.c_int64(), C.c_int64()

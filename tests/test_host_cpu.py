@@ -42,6 +42,25 @@ def test_library_exports_header(built_lib):
     assert built_lib.sacenv_error_string(-2).decode().startswith("Well someone")
 
 
+def test_digest_covers_every_included_file():
+    """Every file a source or header of the library includes by name is an input of the
+    digest (``_build.deps()``); no source is another's header, and no macro cuts one."""
+    from sacenv import _build
+    deps = {os.path.realpath(path) for _, path in _build.deps()}
+    assert len(deps) == len(_build.deps())
+    seen = 0
+    for rel, path in _build.deps():
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+            assert not inc.endswith(".hip"), f"{rel} includes the source {inc}"
+            found = [os.path.join(d, inc) for d in (_build.CSRC, _build.INCLUDE) if os.path.exists(os.path.join(d, inc))]
+            assert found, f"{rel} includes {inc}, which is in neither csrc/ nor include/"
+            assert os.path.realpath(found[0]) in deps, f"{rel} includes {inc}, which deps() does not list"
+            seen += 1
+    assert seen >= len(_build.SOURCES)        # (every source includes at least one of them)
+    for f in sorted(f for f in os.listdir(_build.CSRC) if f.endswith((".hip", ".h"))):
+        assert "BODIES_ONLY" not in open(os.path.join(_build.CSRC, f)).read(), f
+
+
 def test_staged_sampler_argument_errors_without_gpu(built_lib):
     """sacenv_replay_stage_draw / _stage_mark / _sample_staged validate on the host, never launching."""
     from sacenv import _lib
