@@ -581,6 +581,9 @@ __device__ __forceinline__ void trig3(double j, double r, double w, double* sj, 
 // x / c for a per-launch constant c, from r = RN(1/c): Markstein's correction
 // step returns the correctly rounded quotient, i.e. the same double as IEEE
 // division, in 3 dependent FLOPs instead of the ~10 of a full fp64 divide.
+// For finite x only: an infinite x gives NaN (err = fma(-inf, c, inf)) where
+// IEEE division gives inf (the one x that can be infinite, the action, is handled
+// by its caller).
 __device__ __forceinline__ double div_c(double x, double c, double r) {
   const double q = x * r;
   const double err = fma(-q, c, x);
@@ -2249,7 +2252,17 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   // BoatEnv.step :69-73
   t = t_idx ? (double)(index + 1) * p.dt : t + p.dt;  // boat_env.py:69
   const int32_t fuel = p.fuel0 - (index + 1);
-  if (p.test_mode == 0) rudder = rudder + div_c((double)act, 10.0, 0.1);  // action / 10
+  // action / 10. div_c's correction step turns an infinite quotient into NaN,
+  // fma(-inf, 10, inf), where IEEE division keeps it (boat_env.py:73: the rudder is
+  // infinite and breaks): a non-finite action passes through instead, inf / 10 = inf
+  // and NaN / 10 = NaN, behind a wave-uniform branch that is almost never taken
+  if (p.test_mode == 0) {
+    double moved = rudder + div_c((double)act, 10.0, 0.1);
+    if (__builtin_expect(__ballot(!__builtin_isfinite(act)) != 0ull, 0)) {
+      if (!__builtin_isfinite(act)) moved = rudder + (double)act;
+    }
+    rudder = moved;
+  }
   if (!t_idx) EARLY_STORE(U_T, t);
   const bool first = index == 0;  // integrator counter == 0 (control_blocks.py:21-22)
   const double v_x_w = v_x * p.one_minus_wf;
