@@ -13,7 +13,12 @@ as OS processes, three at a time; here they are the members of one ``NativeSACPo
 * an ``EpisodeLog`` on the env; an episode of env e belongs to member e // N.
 
     python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
-        [--replay population|members]
+        [--replay population|members] [--noise torch|counter] [--noise-seed 0]
+
+``--noise counter`` gives member m the noise seed ``--noise-seed`` + m (``sacenv.PolicyNoise``): the
+act draw and both learn draws of an iteration come from one launch for all members, and member m's
+run is the run a stand-alone ``NativeSAC(noise_seed=...)`` on envs [m N, (m + 1) N) makes, bit for
+bit, whatever P is. ``--noise torch`` (the default) draws from torch's device stream.
 
 Prints the members' drawn values (the four numbers a tuned_configs.yaml differs in, one line per
 member), then what main.py:99-114 prints per model -- Score (the last finished episode), Best
@@ -46,6 +51,9 @@ def main(argv=None):
     ap.add_argument("--save", default=None, help="directory for the members' checkpoints")
     ap.add_argument("--replay", choices=("population", "members"), default="population",
                     help="one PopulationReplay for all members, or one DeviceReplayBuffer per member")
+    ap.add_argument("--noise", choices=("torch", "counter"), default="torch",
+                    help="policy noise from torch's stream, or counter-based with one seed per member")
+    ap.add_argument("--noise-seed", type=int, default=0, help="member m's noise seed is this + m")
     args = ap.parse_args(argv)
     P, N = args.members, args.envs_per_member
     if N < 64 or N % 64:
@@ -59,7 +67,8 @@ def main(argv=None):
     replay = None
     if pooled:  # the members' buffers in one arena, with the seeds the per-member buffers get
         replay = PopulationReplay(P, configs[0].max_size, (11,), 1, device=dev, seeds=list(range(P)))
-    pop = NativeSACPopulation(dev, configs, init_seeds=list(range(P)), buffer_seeds=list(range(P)), replay=replay)
+    pop = NativeSACPopulation(dev, configs, init_seeds=list(range(P)), buffer_seeds=list(range(P)), replay=replay,
+                              noise_seeds=[args.noise_seed + m for m in range(P)] if args.noise == "counter" else None)
     for m, mem in enumerate(pop.members):
         print(f"member {m}: " + json.dumps(mem.hpset()))
     env = VecBoatEnv({"base_settings": {"experiment": 6, "test_mode": 0}}, P * N, seed=0, device=dev,
@@ -72,7 +81,10 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.iters):
-        a = pop.choose_action(obs.view(P, N, -1))
+        eps = noise = None
+        if pop.noise is not None:  # the act draw and both learn draws of this iteration: one launch
+            eps, noise = pop.noise_for_step(N)
+        a = pop.choose_action(obs.view(P, N, -1), eps=eps)
         env.step(a.view(-1))
         log.update()
         if pooled:  # member m's rows are envs [m N, (m + 1) N): the env's outputs as they lie
@@ -82,7 +94,7 @@ def main(argv=None):
             pop.remember(m, obs[rows], a[m], env.reward[rows], env.obs[rows], env.term[rows],
                          final_state=env.final_obs[rows], last_term=last_term[m])
         obs = env.obs.clone()
-        out = pop.learn(losses=False)
+        out = pop.learn(noise=noise, losses=False)
         losses = out if out is not None else losses
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
@@ -103,7 +115,7 @@ def main(argv=None):
         pop.save_models(args.save, optimizer=True)
     out = {"pipeline": "population act + VecBoatEnv.step + " + ("population store + population sample" if pooled else
                                                                   "per-member store + per-member sample")
-                       + " + population learn", "replay": args.replay,
+                       + " + population learn", "replay": args.replay, "noise": args.noise,
            "members": P, "envs_per_member": N, "iters": args.iters, "batch": args.batch,
            "env_steps_per_s": P * N * args.iters / el, "ms_per_iter": el / args.iters * 1e3,
            "losses": None if losses is None else losses.tolist(), "table": table}

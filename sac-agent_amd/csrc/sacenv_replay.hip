@@ -20,6 +20,8 @@
 
 #include "sacenv_replay_core.h"
 
+#include "sacenv_philox.h"
+
 namespace {
 
 __global__ void __launch_bounds__(kWave) k_rb_init(RB r, uint32_t seed) { init_body(r, seed); }
@@ -364,23 +366,8 @@ __global__ void __launch_bounds__(256) k_rb_gather_staged(SacenvReplayParams p, 
 // keyed by the seed and counted by (draw, learn, attempt) instead of one
 // MT19937 stream: every draw of every learn is independent of the others, so a
 // segment's seg x batch draws run at once -- no 624-word chain that one
-// workgroup has to walk -- and the thread that draws a row also marks it.
-__device__ __forceinline__ void philox4x64_10(uint64_t c[4], uint64_t k0, uint64_t k1) {
-  constexpr uint64_t kM0 = 0xD2E7470EE14C6C93ull, kM1 = 0xCA5A826395121157ull;  // multipliers
-  constexpr uint64_t kW0 = 0x9E3779B97F4A7C15ull, kW1 = 0xBB67AE8584CAA73Bull;  // Weyl key bumps
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t hi0 = __umul64hi(kM0, c[0]), lo0 = kM0 * c[0];
-    const uint64_t hi1 = __umul64hi(kM1, c[2]), lo1 = kM1 * c[2];
-    const uint64_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = lo1;
-    c[2] = n2;
-    c[3] = lo0;
-    k0 += kW0;
-    k1 += kW1;
-  }
-}
+// workgroup has to walk -- and the thread that draws a row also marks it. The generator
+// itself is sacenv_philox.h's (the policy noise of sacenv_noise.hip shares it).
 
 // Draw i of global learn L over [0, rng]: word i % 4 of the Philox4x64-10 blocks at
 // counters (i / 4, L, j, 0) under key (seed, 0), j = 0, 1, ...: the first whose bits

@@ -9,7 +9,8 @@ from .config import BoatConfig
 from .spaces import Box
 
 __all__ = ["BoatConfig", "Box", "VecBoatEnv", "BoatEnv", "ParachuteEnv", "CarEnv", "VecToyEnv",
-           "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "PopulationReplay", "_lib"]
+           "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "PopulationReplay", "PolicyNoise",
+           "_lib"]
 
 
 def __getattr__(name):  # lazy: importing torch-dependent classes only when used
@@ -28,4 +29,7 @@ def __getattr__(name):  # lazy: importing torch-dependent classes only when used
     if name == "PopulationReplay":
         from .population_replay import PopulationReplay
         return PopulationReplay
+    if name == "PolicyNoise":
+        from .noise import PolicyNoise
+        return PolicyNoise
     raise AttributeError(name)

@@ -206,6 +206,21 @@ class ReplayPopLayout(C.Structure):
     _fields_ = [("member_bytes", _i64), ("total_bytes", _i64), ("max_members", _i32), ("pad", _i32)]
 
 
+# include/sacenv_noise.h (SACENV_NOISE_VERSION 1): counter-based policy noise for every member
+# and up to four draws in one launch; beside the ABI of sacenv.h, bound only where the library has it
+NOISE_VERSION = 1
+NOISE_MAX_MEMBERS = 64
+NOISE_MAX_STREAMS = 4
+NOISE_KEY1 = 0x6E6F697365
+NOISE_ACT, NOISE_LEARN1, NOISE_LEARN2 = 0, 1, 2
+NOISE_EXPORTS = ("sacenv_noise_normal",)
+
+
+class NoiseDraw(C.Structure):
+    """SacenvNoiseDraw (sacenv_noise.h): rows first_call .. first_call + calls - 1 of one stream."""
+    _fields_ = [("stream", C.c_uint64), ("first_call", C.c_uint64), ("calls", _i32), ("n", _i32), ("out", _p)]
+
+
 _LIB = None
 
 
@@ -311,7 +326,8 @@ def load(path: str | None = None):
             [RP, _i32, C.POINTER(ReplayPopLayout)], [RP, _i32, _p, C.POINTER(C.c_uint32), _p],
             [RP, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
             [RP, _i32, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p],
-            [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])))
+            [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])),
+        (NOISE_EXPORTS, ([_i32, C.POINTER(C.c_uint64), _i32, C.POINTER(NoiseDraw), _p],)))
     for names, argtypes in optional:
         assert len(names) == len(argtypes)
         for name, args in zip(names, argtypes):

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from .agent import AgentConfig, VecSAC, load_models, save_models
+from .noise import ACT, LEARN1, LEARN2, PolicyNoise
 from .sac_native import NativeSAC, _set_param
 
 _COMMON = ("batch_size", "layer1_size", "layer2_size", "max_size")
@@ -96,12 +97,22 @@ class PopulationMember:
     def adam_step(self) -> int:
         return self.population.adam_step
 
+    @property
+    def act_calls(self) -> int:
+        return self.population.act_calls
+
+    @property
+    def noise_seed(self):
+        seeds = self.population.noise_seeds
+        return None if seeds is None else seeds[self.index]
+
     def load_optimizer_state(self, state: dict) -> None:
         for n in self.NETS[:4]:
             for which, views in self.adam_state(n).items():
                 for k, v in views.items():
                     v.copy_(state[f"{n}.{which}.{k}"].reshape(v.shape))
         self.loaded_step = int(state["step"])  # the population commits it (one step for all members)
+        self.loaded_act_calls = int(state["act_calls"]) if "act_calls" in state else None
 
     def hpset(self) -> dict:
         """The four searched values under the reference's config keys (tuned_configs.yaml)."""
@@ -115,7 +126,7 @@ class NativeSACPopulation:
 
     def __init__(self, device, configs, *, obs_dim: int = 11, max_action: float = 1.0, init_seeds=None,
                  buffer_seeds=None, with_memory: bool = True, adam_eps: float = 1e-8, replay=None,
-                 _build: bool = True):
+                 noise_seeds=None, _build: bool = True):
         cfgs = _common_configs(configs)
         P = self.P = len(cfgs)
         cfg = cfgs[0]
@@ -123,7 +134,8 @@ class NativeSACPopulation:
             raise ValueError(f"the SAC kernels are built for {_lib.SAC_HIDDEN}-wide layers")
         if P > _lib.POPULATION_MAX_MEMBERS:
             raise ValueError(f"a population holds at most {_lib.POPULATION_MAX_MEMBERS} members, got {P}")
-        for name, seeds in (("init_seeds", init_seeds), ("buffer_seeds", buffer_seeds)):
+        for name, seeds in (("init_seeds", init_seeds), ("buffer_seeds", buffer_seeds),
+                            ("noise_seeds", noise_seeds)):
             if seeds is not None and len(seeds) != P:
                 raise ValueError(f"{name} must hold one seed per member")
         dev = torch.device(device)
@@ -158,6 +170,13 @@ class NativeSACPopulation:
         self.scratch = torch.empty(PL.total_scratch_bytes // 4, dtype=torch.float32, device=self.device)
         self.losses = torch.zeros((P, 4), dtype=torch.float32, device=self.device)
         self.adam_step = 0
+        # counter-based policy noise (sacenv/noise.py), one seed per member: member m draws what a
+        # NativeSAC(noise_seed=noise_seeds[m]) draws; one act_calls for all, as one adam_step
+        self.noise_seeds = None if noise_seeds is None else tuple(int(s) for s in noise_seeds)
+        self.noise = None
+        if noise_seeds is not None:
+            self.noise = PolicyNoise(self.noise_seeds, self.device)
+        self.act_calls = 0
         self.members = [PopulationMember(self, m, cfgs[m], None if init_seeds is None else init_seeds[m], _build)
                         for m in range(P)]
         if _build:
@@ -204,12 +223,35 @@ class NativeSACPopulation:
         if obs.dim() != 3 or obs.shape[0] != self.P or obs.shape[2] != D:
             raise ValueError(f"obs must be [{self.P}, n, {D}], got {list(obs.shape)}")
         n = obs.shape[1]
-        eps = torch.randn((self.P, n), device=self.device) if eps is None else self._f32(eps, self.P * n, "eps")
+        if eps is not None:
+            eps = self._f32(eps, self.P * n, "eps")
+        elif self.noise is not None:
+            eps = self.noise.normal(ACT, self.act_calls, n)[0]
+        else:
+            eps = torch.randn((self.P, n), device=self.device)
         out = torch.empty((self.P, n, 1), dtype=torch.float32, device=self.device)
         _lib.check(self._native().sacenv_sac_pop_act(C.byref(self.params), self.P, self.weights.data_ptr(),
                                                   obs.data_ptr(), n, eps.data_ptr(), out.data_ptr(), None,
                                                   self._stream()))
+        self.act_calls += 1  # every accepted call is one act, wherever its eps came from
         return out
+
+    def noise_for_step(self, n: int):
+        """``(eps [P, n], (e1, e2) [P, B] each)``: what the next ``choose_action`` on n rows per
+        member and the next ``learn`` would draw, from one launch; changes no state."""
+        if self.noise is None:
+            raise RuntimeError("noise_for_step needs a population built with noise_seeds")
+        B = self.configs[0].batch_size
+        eps, e1, e2 = self.noise.draw([(ACT, self.act_calls, n), (LEARN1, self.adam_step, B),
+                                       (LEARN2, self.adam_step, B)])
+        return eps[0], (e1[0], e2[0])
+
+    def act_noise(self, K: int, n: int) -> torch.Tensor:
+        """f32 [K, P, n]: row k is what the k-th ``choose_action`` from now would draw; changes
+        no state."""
+        if self.noise is None:
+            raise RuntimeError("act_noise needs a population built with noise_seeds")
+        return self.noise.normal(ACT, self.act_calls, n, calls=K)
 
     def remember(self, m: int, state, action, reward, new_state, code, **kw) -> None:
         """``memory[m].store_batch``: member m's transitions. (With a ``PopulationReplay`` the
@@ -253,10 +295,12 @@ class NativeSACPopulation:
         done = torch.as_tensor(done, device=self.device).to(torch.uint8).contiguous()
         if reward.numel() != P * B or reward.shape[0] != P or done.numel() != P * B or done.shape[0] != P:
             raise ValueError(f"reward and done must be [{P}, {B}], got {list(reward.shape)} and {list(done.shape)}")
-        if noise is None:
-            e1, e2 = torch.randn((P, B), device=self.device), torch.randn((P, B), device=self.device)
-        else:
+        if noise is not None:
             e1, e2 = self._f32(noise[0], P * B, "noise[0]"), self._f32(noise[1], P * B, "noise[1]")
+        elif self.noise is not None:
+            e1, e2 = (t[0] for t in self.noise.draw([(LEARN1, self.adam_step, B), (LEARN2, self.adam_step, B)]))
+        else:
+            e1, e2 = torch.randn((P, B), device=self.device), torch.randn((P, B), device=self.device)
         step = self.adam_step + 1  # committed only once the call is accepted
         _lib.check(self._native().sacenv_sac_pop_learn(
             C.byref(self.params), P, self._hp, self.weights.data_ptr(), self.scratch.data_ptr(),
@@ -268,17 +312,21 @@ class NativeSACPopulation:
     # ---- members in and out
 
     def export_member(self, m: int) -> NativeSAC:
-        """A stand-alone ``NativeSAC`` with member m's weights, Adam moments and step (a copy)."""
+        """A stand-alone ``NativeSAC`` with member m's weights, Adam moments, step, noise seed and
+        act count (a copy)."""
         agent = NativeSAC(self.device, self.configs[m], obs_dim=self.params.obs_dim,
-                          max_action=self.params.max_action, with_memory=False, adam_eps=self.params.adam_eps)
+                          max_action=self.params.max_action, with_memory=False, adam_eps=self.params.adam_eps,
+                          noise_seed=None if self.noise_seeds is None else self.noise_seeds[m])
         agent.weights.copy_(self.weights[m, : agent.weights.numel()])
         agent.adam_step = self.adam_step
+        agent.act_calls = self.act_calls
         return agent
 
     @classmethod
     def from_agents(cls, agents, *, with_memory: bool = False, buffer_seeds=None) -> "NativeSACPopulation":
-        """The population whose member m is a copy of ``agents[m]`` (weights, Adam moments, step).
-        The agents must agree in everything the members share, and in their step."""
+        """The population whose member m is a copy of ``agents[m]`` (weights, Adam moments, step,
+        noise seed). The agents must agree in everything the members share, in their step, and --
+        seeded agents (all or none) -- in their act count."""
         agents = list(agents)
         if not agents:
             raise ValueError("a population needs at least one member")
@@ -291,11 +339,17 @@ class NativeSACPopulation:
                 raise ValueError(f"the agents differ in their Adam step ({a.adam_step} != {a0.adam_step})")
             if a.device != a0.device:
                 raise ValueError("the agents live on different devices")
+            if (a.noise_seed is None) != (a0.noise_seed is None):
+                raise ValueError("either every agent has a noise seed or none has")
+            if a0.noise_seed is not None and a.act_calls != a0.act_calls:
+                raise ValueError(f"the agents differ in their act count ({a.act_calls} != {a0.act_calls})")
         pop = cls(a0.device, [a.cfg for a in agents], obs_dim=a0.params.obs_dim, max_action=a0.params.max_action,
-                  with_memory=with_memory, buffer_seeds=buffer_seeds, adam_eps=a0.params.adam_eps, _build=False)
+                  with_memory=with_memory, buffer_seeds=buffer_seeds, adam_eps=a0.params.adam_eps,
+                  noise_seeds=None if a0.noise_seed is None else [a.noise_seed for a in agents], _build=False)
         for m, a in enumerate(agents):
             pop.weights[m, : a.weights.numel()].copy_(a.weights)
         pop.adam_step = a0.adam_step
+        pop.act_calls = a0.act_calls
         return pop
 
     def state_dicts(self) -> list:
@@ -309,15 +363,21 @@ class NativeSACPopulation:
             save_models(mem, os.path.join(experiment_dir, f"member_{m}"), optimizer)
 
     def load_models(self, experiment_dir: str, optimizer: bool = False) -> None:
-        steps = set()
+        steps, acts = set(), set()
         for m, mem in enumerate(self.members):
             load_models(mem, os.path.join(experiment_dir, f"member_{m}"), optimizer)
             if optimizer:
                 steps.add(mem.loaded_step)
+                if self.noise_seeds is not None and mem.loaded_act_calls is not None:
+                    acts.add(mem.loaded_act_calls)
         if len(steps) > 1:
             raise ValueError(f"the members' checkpoints differ in their Adam step: {sorted(steps)}")
+        if len(acts) > 1:
+            raise ValueError(f"the members' checkpoints differ in their act count: {sorted(acts)}")
         if steps:
             self.adam_step = steps.pop()
+        if acts:
+            self.act_calls = acts.pop()
         self.sync()
 
 

@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from . import _lib
 from .agent import AgentConfig, VecSAC, load_models, save_models
+from .noise import ACT, LEARN1, LEARN2, PolicyNoise
 
 # torch parameter names per net, in the C layout's tensor order (w1, b1, w2, b2, head 0, head 1)
 _TENSORS = {
@@ -51,7 +52,7 @@ class NativeSAC:
 
     def __init__(self, device, config=None, *, obs_dim: int = 11, n_actions: int = 1,
                  max_action: float = 1.0, init_seed: int | None = None, buffer_seed: int = 0,
-                 with_memory: bool = True, adam_eps: float = 1e-8):
+                 with_memory: bool = True, adam_eps: float = 1e-8, noise_seed: int | None = None):
         cfg = self.cfg = AgentConfig.from_any(config)
         if cfg.layer1_size != _lib.SAC_HIDDEN or cfg.layer2_size != _lib.SAC_HIDDEN:
             raise ValueError(f"the SAC kernels are built for {_lib.SAC_HIDDEN}-wide layers")
@@ -81,6 +82,13 @@ class NativeSAC:
                 _set_param(m, pname, view)
             setattr(self, name, m.to(self.device))
         self.adam_step = 0
+        # counter-based policy noise (sacenv/noise.py): with a seed, the draws of choose_action
+        # and learn are a function of (seed, act_calls / adam_step) alone; without, torch's stream
+        self.noise_seed = None if noise_seed is None else int(noise_seed)
+        self.noise = None
+        if noise_seed is not None:
+            self.noise = PolicyNoise([noise_seed], self.device)
+        self.act_calls = 0
         self.sync()
         self.memory = None
         if with_memory:
@@ -142,11 +150,38 @@ class NativeSAC:
         if obs.dim() != 2 or obs.shape[1] != self.params.obs_dim:
             raise ValueError(f"obs must be [N, {self.params.obs_dim}], got {tuple(obs.shape)}")
         n = obs.shape[0]
-        eps = torch.randn(n, device=self.device) if eps is None else self._f32(eps, n)
+        if eps is not None:
+            eps = self._f32(eps, n)
+        elif self.noise is not None:
+            eps = self.noise.normal(ACT, self.act_calls, n).view(n)
+        else:
+            eps = torch.randn(n, device=self.device)
         out = torch.empty((n, 1), dtype=torch.float32, device=self.device)
         _lib.check(_lib.load().sacenv_sac_act(C.byref(self.params), self.weights.data_ptr(), obs.data_ptr(),
                                               n, eps.data_ptr(), out.data_ptr(), None, self._stream()))
+        self.act_calls += 1  # every accepted call is one act, wherever its eps came from
         return out
+
+    def _learn_noise(self, B):
+        e1, e2 = self.noise.draw([(LEARN1, self.adam_step, B), (LEARN2, self.adam_step, B)])
+        return e1.view(B), e2.view(B)
+
+    def noise_for_step(self, n: int):
+        """``(eps, (e1, e2))``: what the next ``choose_action`` on n rows and the next ``learn``
+        would draw, from one launch; changes no state (pass them as ``eps=`` and ``noise=``)."""
+        if self.noise is None:
+            raise RuntimeError("noise_for_step needs an agent built with noise_seed")
+        B = self.cfg.batch_size
+        eps, e1, e2 = self.noise.draw([(ACT, self.act_calls, n), (LEARN1, self.adam_step, B),
+                                       (LEARN2, self.adam_step, B)])
+        return eps.view(n), (e1.view(B), e2.view(B))
+
+    def act_noise(self, K: int, n: int) -> torch.Tensor:
+        """f32 [K, n]: row k is what the k-th ``choose_action`` from now would draw (the table
+        ``ClosedLoop.run`` takes); changes no state."""
+        if self.noise is None:
+            raise RuntimeError("act_noise needs an agent built with noise_seed")
+        return self.noise.normal(ACT, self.act_calls, n, calls=K).view(K, n)
 
     @torch.no_grad()
     def choose_action_handoff(self, obs, eps, out, *, obs_ready, obs_want: int, act_ready, act_value: int,
@@ -185,10 +220,12 @@ class NativeSAC:
         done = torch.as_tensor(done, device=self.device).to(torch.uint8).contiguous()
         if reward.numel() != B or done.numel() != B:
             raise ValueError("reward and done must hold one value per batch row")
-        if noise is None:
-            e1, e2 = torch.randn(B, device=self.device), torch.randn(B, device=self.device)
-        else:
+        if noise is not None:
             e1, e2 = self._f32(noise[0], B), self._f32(noise[1], B)
+        elif self.noise is not None:
+            e1, e2 = self._learn_noise(B)
+        else:
+            e1, e2 = torch.randn(B, device=self.device), torch.randn(B, device=self.device)
         step = self.adam_step + 1  # committed only once the call is accepted
         _lib.check(_lib.load().sacenv_sac_learn(
             C.byref(self.params), self.weights.data_ptr(), self.scratch.data_ptr(), state.data_ptr(),
@@ -206,6 +243,8 @@ class NativeSAC:
     def optimizer_state(self) -> dict:
         """The Adam moments of the four optimised nets and the step count (CPU copies)."""
         out = {"step": torch.tensor(self.adam_step, dtype=torch.int64)}
+        if self.noise_seed is not None:  # the act draw's call count: a resumed agent draws on
+            out["act_calls"] = torch.tensor(self.act_calls, dtype=torch.int64)
         for n in self.NETS[:4]:
             for which, views in self.adam_state(n).items():
                 out.update({f"{n}.{which}.{k}": v.detach().cpu().clone() for k, v in views.items()})
@@ -217,6 +256,8 @@ class NativeSAC:
                 for k, v in views.items():
                     v.copy_(state[f"{n}.{which}.{k}"].reshape(v.shape))
         self.adam_step = int(state["step"])
+        if self.noise_seed is not None and "act_calls" in state:
+            self.act_calls = int(state["act_calls"])
 
     def save_models(self, experiment_dir: str, optimizer: bool = False) -> None:
         """ContinuousAgent.save_models (continuous_agent.py:79-84), the reference's files."""
