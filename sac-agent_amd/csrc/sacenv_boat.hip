@@ -755,12 +755,20 @@ __device__ __forceinline__ void interval_extrema_on(const SacenvBoatParams& p, c
   if (fabs(qa) <= 1e-14 * scale) {
     if (qb != 0.0) r0 = -qc * __builtin_amdgcn_rcp(qb);
   } else {
-    const double disc = qb * qb - 4.0 * qa * qc;
+    // a tiny curve's quadratic (knots below 1e-150: the squares would underflow) scaled
+    // by a power of two to scale in [0.5, 1): the same roots. ldexp on each coefficient
+    // is exact down to subnormal knots (the factor itself can pass 2^1023)
+    double sa = qa, sb = qb, sc = qc;
+    if (scale < 0x1p-500) {
+      const int up = -__builtin_amdgcn_frexp_exp(scale);
+      sa = ldexp(qa, up), sb = ldexp(qb, up), sc = ldexp(qc, up);
+    }
+    const double disc = sb * sb - 4.0 * sa * sc;
     if (disc >= 0.0) {
       const double sq = disc > 0.0 ? disc * __builtin_amdgcn_rsq(disc) : 0.0;
-      const double q = -0.5 * (qb + copysign(sq, qb));
-      r0 = q * __builtin_amdgcn_rcp(qa);
-      if (q != 0.0) r1 = qc * __builtin_amdgcn_rcp(q);
+      const double q = -0.5 * (sb + copysign(sq, sb));
+      r0 = q * __builtin_amdgcn_rcp(sa);
+      if (q != 0.0) r1 = sc * __builtin_amdgcn_rcp(q);
     }
   }
   const bool ok0 = r0 > -0.01 && r0 < 1.01, ok1 = r1 > -0.01 && r1 < 1.01;

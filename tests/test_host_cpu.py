@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from interval_extrema import interval_extrema_py as _interval_extrema_py  # (the mirror lives in oracle/)
 
 HEADER = os.path.join(ROOT, "include", "sacenv.h")
 
@@ -438,44 +439,6 @@ def test_spline_g_equals_scipy_basis():
         val = (u[:, None] * E[j] + t[:, None] * E[j + 1]
                + (u ** 3 - u)[:, None] * M[j] + (t ** 3 - t)[:, None] * M[j + 1])
         np.testing.assert_allclose(val, B, rtol=0, atol=2e-14)
-
-
-def _interval_extrema_py(y, m, n, L, j):
-    """Python mirror of the kernel's interval_extrema candidate rule -> grid indices."""
-    step = (n - 1) / (L - 1)
-    jf = lambda i: min(int(i * step), n - 2)
-
-    inv = (L - 1) / (n - 1)        # the host's knot_inv (sacenv/config.py)
-    lo = max(math.ceil(j * inv) - 1, 0)
-    while lo < L and jf(lo) < j:
-        lo += 1
-    hi = min(math.floor((j + 1) * inv) + 1, L - 1)
-    while hi >= 0 and jf(hi) > j:
-        hi -= 1
-    if lo > hi:
-        return [], []
-    cand = [lo, hi]
-    a, b = m[j], m[j + 1]
-    qa, qb, qc = 3 * (b - a), 6 * a, y[j + 1] - y[j] - 2 * a - b
-    roots = []
-    scale = abs(qa) + abs(qb) + abs(qc)
-    if abs(qa) <= 1e-14 * scale:
-        if qb != 0:
-            roots.append(-qc / qb)
-    else:
-        disc = qb * qb - 4 * qa * qc
-        if disc >= 0:
-            q = -0.5 * (qb + math.copysign(math.sqrt(disc), qb if qb != 0 else 1.0))
-            roots.append(q / qa)
-            if q != 0:
-                roots.append(qc / q)
-    for tr in roots:
-        if not (-0.01 < tr < 1.01):
-            continue
-        i0 = math.floor((j + tr) * inv)
-        for d in (-1, 0, 1, 2):
-            cand.append(min(max(i0 + d, lo), hi))
-    return cand, (lo, hi)
 
 
 def test_interval_bound_starts_never_overshoot():
