@@ -1,7 +1,7 @@
 """Python mirror of the kernel's grid-extrema candidate rule -- TEST INFRASTRUCTURE,
 NOT PRODUCT CODE.
 
-``interval_extrema_on`` (sacenv_boat.hip) finds the extreme grid samples of one spline
+``interval_extrema_on`` (sacenv_boat_wind.h) finds the extreme grid samples of one spline
 interval among ten candidates: the interval's first and last grid index and the four
 neighbours of each critical point. This is that rule in float64 Python (exact ``sqrt``
 and division where the kernel uses approximations), returning the candidate indices.

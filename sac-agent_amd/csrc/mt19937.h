@@ -1,8 +1,43 @@
 // mt19937.h — numpy-legacy MT19937 (numpy/random/src/mt19937, pinned numpy
-// 1.23.5) for one wave64: lane-parallel twist in LDS, 64-word windows.
-// Included INSIDE an anonymous namespace of each .hip translation unit (after
-// kWave and the kMt* constants); the LDS type L has `uint32_t blk[2][624]`.
+// 1.23.5) for one wave64: lane-parallel twist in LDS, 64-word windows, and the
+// legacy generator's bounded-integer mask and 53-bit double.
+// Included at file scope, after the includer's kWave (the wave size its kernels are
+// written for); the LDS type L has `uint32_t blk[2][624]`.
 #pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sacenv.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kMtN = SACENV_MT_N;
+constexpr int kMtM = 397;
+constexpr uint32_t kMtUpper = 0x80000000u;
+constexpr uint32_t kMtLower = 0x7fffffffu;
+constexpr uint32_t kMtMatrixA = 0x9908b0dfu;
+
+// the smallest 2^k - 1 >= rng: masked rejection on 32-bit words (numpy
+// random_bounded_uint64_fill -> buffered_bounded_masked_uint32) accepts a word w
+// when (w & mask) <= rng
+__device__ __forceinline__ uint32_t range_mask32(uint32_t rng) {
+  uint32_t mask = rng;
+  mask |= mask >> 1;
+  mask |= mask >> 2;
+  mask |= mask >> 4;
+  mask |= mask >> 8;
+  mask |= mask >> 16;
+  return mask;
+}
+
+// np.random.sample: legacy_double = genrand_res53 on two consecutive tempered words
+__device__ __forceinline__ double res53(uint32_t wa, uint32_t wb) {
+  const double a = (double)(wa >> 5), b = (double)(wb >> 6);
+  return (a * 67108864.0 + b) / 9007199254740992.0;
+}
 
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
   y ^= (y >> 11);
@@ -85,3 +120,4 @@ __device__ void mt_finish(MtStream& st, L& l, int32_t* gpos, int lane) {
   if (lane == 0) *gpos = st.pos;
 }
 
+}  // namespace

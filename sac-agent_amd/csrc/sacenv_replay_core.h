@@ -12,15 +12,12 @@
 #include "sacenv.h"
 
 namespace {
-
 constexpr int kWave = 64;
-constexpr int kMtN = SACENV_MT_N;
-constexpr int kMtM = 397;
-constexpr uint32_t kMtUpper = 0x80000000u;
-constexpr uint32_t kMtLower = 0x7fffffffu;
-constexpr uint32_t kMtMatrixA = 0x9908b0dfu;
+}  // namespace
 
 #include "mt19937.h"
+
+namespace {
 
 __host__ __device__ inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 

@@ -18,7 +18,9 @@ BUILD = os.path.join(PKG_ROOT, "build")
 LIB = os.path.join(BUILD, "libsacenv.so")
 SOURCES = ("sacenv_boat.hip", "sacenv_replay.hip", "sacenv_sac.hip", "sacenv_episodes.hip",
            "sacenv_sac_pop.hip", "sacenv_replay_pop.hip", "sacenv_noise.hip")
-HEADERS = ("mt19937.h", "sacenv_replay_core.h", "sacenv_sac_core.h", "sacenv_philox.h")
+HEADERS = ("mt19937.h", "sacenv_replay_core.h", "sacenv_sac_core.h", "sacenv_philox.h",
+           "sacenv_boat_arena.h", "sacenv_boat_math.h", "sacenv_boat_wind.h", "sacenv_boat_draw.h",
+           "sacenv_toys.h", "sacenv_boat_owner.h")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fPIC", "-shared", "-Wall")
 

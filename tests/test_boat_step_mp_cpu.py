@@ -9,7 +9,7 @@ on the step kernel's hand-written polynomials. No GPU.
 * ``C_REF`` in oracle/boat_step_cases.py equals profiles/r14_boat_step_margins.json;
 * the source guard (``test_kernel_polynomials``): the ``sn``, ``cs``, ``ex`` and ``ec``
   literals and the three Cody-Waite constants are read out of
-  sac-agent_amd/csrc/sacenv_boat.hip by regex, the kernel's Horner schemes are
+  sac-agent_amd/csrc/sacenv_boat_math.h by regex, the kernel's Horner schemes are
   evaluated operation for operation with a correctly rounded fma (exact mpmath
   product and sum, rounded once), and compared with mpmath's sin / cos / exp.
   Bars: a one-off run of this check on the literals of the commit that introduced
@@ -37,7 +37,7 @@ import boat_step_mp as M
 from boat_oracle import (TERM_FUEL, TERM_GOAL, TERM_NONE, TERM_OOB, TERM_RUDDER, TERM_TIMEOUT)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIP = os.path.join(ROOT, "sac-agent_amd", "csrc", "sacenv_boat.hip")
+HIP = os.path.join(ROOT, "sac-agent_amd", "csrc", "sacenv_boat_math.h")
 
 SIN_TAYLOR_BAR, SINCOS_BAR, EXP_BAR = 1.1, 1.45, 0.95
 

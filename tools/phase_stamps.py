@@ -5,7 +5,7 @@ loaded by the product path), runs the bench workload (exp 6, 65 536 envs,
 500-step episodes, 128-step segments, no refill between the two measured
 segments) and reads the per-wave phase sums the k_rollout owner waves write
 into the (otherwise unused) accel region: shader clocks (s_memtime) between
-sched-barrier-pinned points of the step (sacenv_boat.hip PHASE):
+sched-barrier-pinned points of the step (sacenv_boat_owner.h PHASE):
 
   1 wind: action, wind piece, trig3 (sin J, sin rudder, sincos wind angle)
   2 dynamics: forces, velocities, yaw, sincos yaw, positions
