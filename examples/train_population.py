@@ -13,7 +13,7 @@ as OS processes, three at a time; here they are the members of one ``NativeSACPo
 * an ``EpisodeLog`` on the env; an episode of env e belongs to member e // N.
 
     python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
-        [--replay population|members] [--noise torch|counter] [--noise-seed 0]
+        [--replay population|members] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
 
 ``--noise counter`` gives member m the noise seed ``--noise-seed`` + m (``sacenv.PolicyNoise``): the
 act draw and both learn draws of an iteration come from one launch for all members, and member m's
@@ -23,7 +23,13 @@ bit, whatever P is. ``--noise torch`` (the default) draws from torch's device st
 Prints the members' drawn values (the four numbers a tuned_configs.yaml differs in, one line per
 member), then what main.py:99-114 prints per model -- Score (the last finished episode), Best
 Score, Average over the look-back -- and one JSON line with the same. ``--save DIR`` writes every
-member's checkpoints to DIR/member_<m>/checkpoints/.
+member's checkpoints to DIR/member_<m>/checkpoints/: the members' LAST weights.
+
+``--keep-best DIR`` keeps what the reference would have on disk instead: it saves a model whenever
+an episode's score beats the look-back average (main.py:106-108). A ``MemberScoreboard`` follows
+the episode log on the device, is updated after every ``learn`` and snapshots the weights of the
+members the rule selects; at the end its table is printed beside the post-hoc one, and the
+snapshots go to DIR/member_<m>/checkpoints/ with DIR/overview.csv (main.py:121-128).
 """
 from __future__ import annotations
 
@@ -54,6 +60,10 @@ def main(argv=None):
     ap.add_argument("--noise", choices=("torch", "counter"), default="torch",
                     help="policy noise from torch's stream, or counter-based with one seed per member")
     ap.add_argument("--noise-seed", type=int, default=0, help="member m's noise seed is this + m")
+    ap.add_argument("--keep-best", default=None, metavar="DIR",
+                    help="snapshot a member whenever an episode of its beats the look-back average; write the "
+                         "snapshots and overview.csv to DIR")
+    ap.add_argument("--max-episode-steps", type=int, default=500)
     args = ap.parse_args(argv)
     P, N = args.members, args.envs_per_member
     if N < 64 or N % 64:
@@ -72,9 +82,13 @@ def main(argv=None):
     for m, mem in enumerate(pop.members):
         print(f"member {m}: " + json.dumps(mem.hpset()))
     env = VecBoatEnv({"base_settings": {"experiment": 6, "test_mode": 0}}, P * N, seed=0, device=dev,
-                     max_episode_steps=500)
+                     max_episode_steps=args.max_episode_steps)
     obs = env.reset().clone()
     log = EpisodeLog(env)
+    board = None
+    if args.keep_best:
+        from sacenv import MemberScoreboard
+        board = MemberScoreboard(log, P, N, lookback=args.lookback, population=pop)
     # terminal as main.py:83-88 stores it: each env's last termination, kept per member
     last_term = [torch.zeros(N, dtype=torch.uint8, device=dev) for _ in range(P)]
     losses = None
@@ -96,11 +110,14 @@ def main(argv=None):
         obs = env.obs.clone()
         out = pop.learn(noise=noise, losses=False)
         losses = out if out is not None else losses
+        if board is not None:  # after learn: where main.py:106 saves
+            board.update()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    entries = log.drain()
+    entries = log.drain()  # (the board reads what is left first)
     owner = entries["env"] // N
     table = []
+    fmt = lambda x: f"{x:12.2f}" if x is not None else f"{'-':>12}"  # noqa: E731
     print(f"{'member':>6} {'episodes':>8} {'Score':>12} {'Best Score':>12} {'Average':>12}")
     for m in range(P):
         scores = entries["score"][owner == m]
@@ -108,17 +125,36 @@ def main(argv=None):
                "score": float(scores[-1]) if scores.size else None,
                "best_score": float(scores.max()) if scores.size else None,
                "avg_score": float(np.mean(scores[-args.lookback:])) if scores.size else None}
+        if board is not None:  # the save rule post hoc, as main.py:99-108 words it
+            ends, history, saves, last_save = entries["end_step"][owner == m], [], 0, None
+            for score, end in zip(scores.tolist(), ends.tolist()):
+                history.append(score)
+                if score > np.mean(history[-args.lookback:]):
+                    saves, last_save = saves + 1, end
+            row.update(saves=saves, last_save_step=last_save)
         table.append(row)
-        fmt = lambda x: f"{x:12.2f}" if x is not None else f"{'-':>12}"  # noqa: E731
         print(f"{m:>6} {row['episodes']:>8} {fmt(row['score'])} {fmt(row['best_score'])} {fmt(row['avg_score'])}")
     if args.save:
         pop.save_models(args.save, optimizer=True)
+    device_table = kept = None
+    if board is not None:
+        device_table = board.table()
+        print("on the device:")
+        print(f"{'member':>6} {'episodes':>8} {'Score':>12} {'Best Score':>12} {'Average':>12} {'saves':>6} "
+              f"{'last save':>10}")
+        for row in device_table:
+            print(f"{row['member']:>6} {row['episodes']:>8} {fmt(row['score'])} {fmt(row['best_score'])} "
+                  f"{fmt(row['avg_score'])} {row['saves']:>6} {str(row['last_save_step']):>10}")
+        kept = board.save_models(args.keep_best)
+        print(f"best member {board.best_member()}; snapshots of members {kept} in {args.keep_best}")
     out = {"pipeline": "population act + VecBoatEnv.step + " + ("population store + population sample" if pooled else
                                                                   "per-member store + per-member sample")
                        + " + population learn", "replay": args.replay, "noise": args.noise,
            "members": P, "envs_per_member": N, "iters": args.iters, "batch": args.batch,
            "env_steps_per_s": P * N * args.iters / el, "ms_per_iter": el / args.iters * 1e3,
            "losses": None if losses is None else losses.tolist(), "table": table}
+    if board is not None:
+        out.update(device_table=device_table, kept=kept, best_member=board.best_member())
     print(json.dumps(out))
     return out
 

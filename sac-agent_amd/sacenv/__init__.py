@@ -10,7 +10,7 @@ from .spaces import Box
 
 __all__ = ["BoatConfig", "Box", "VecBoatEnv", "BoatEnv", "ParachuteEnv", "CarEnv", "VecToyEnv",
            "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "PopulationReplay", "PolicyNoise",
-           "_lib"]
+           "MemberScoreboard", "_lib"]
 
 
 def __getattr__(name):  # lazy: importing torch-dependent classes only when used
@@ -32,4 +32,7 @@ def __getattr__(name):  # lazy: importing torch-dependent classes only when used
     if name == "PolicyNoise":
         from .noise import PolicyNoise
         return PolicyNoise
+    if name == "MemberScoreboard":
+        from .scoreboard import MemberScoreboard
+        return MemberScoreboard
     raise AttributeError(name)

@@ -20,7 +20,7 @@ SOURCES = ("sacenv_boat.hip", "sacenv_replay.hip", "sacenv_sac.hip", "sacenv_epi
            "sacenv_sac_pop.hip", "sacenv_replay_pop.hip", "sacenv_noise.hip")
 HEADERS = ("mt19937.h", "sacenv_replay_core.h", "sacenv_sac_core.h", "sacenv_philox.h",
            "sacenv_boat_arena.h", "sacenv_boat_math.h", "sacenv_boat_wind.h", "sacenv_boat_draw.h",
-           "sacenv_toys.h", "sacenv_boat_owner.h")
+           "sacenv_toys.h", "sacenv_boat_owner.h", "sacenv_board_core.h")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fPIC", "-shared", "-Wall")
 
@@ -29,7 +29,8 @@ def deps() -> list[tuple[str, str]]:
     """(path relative to the repo root, absolute path) of every input file."""
     rel = [os.path.join("sac-agent_amd", "csrc", f) for f in SOURCES + HEADERS]
     rel += [os.path.join("include", h) for h in ("sacenv.h", "sacenv_episodes.h", "sacenv_population.h",
-                                                    "sacenv_population_replay.h", "sacenv_noise.h")]
+                                                    "sacenv_population_replay.h", "sacenv_noise.h",
+                                                    "sacenv_scoreboard.h")]
     return [(r, os.path.join(REPO_ROOT, r)) for r in rel]
 
 

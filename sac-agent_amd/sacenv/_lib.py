@@ -221,6 +221,30 @@ class NoiseDraw(C.Structure):
     _fields_ = [("stream", C.c_uint64), ("first_call", C.c_uint64), ("calls", _i32), ("n", _i32), ("out", _p)]
 
 
+# include/sacenv_scoreboard.h (SACENV_SCOREBOARD_VERSION 1): per-member scores, the look-back mean
+# and the save rule from the episode log; beside the ABI of sacenv.h, bound only where the library
+# has them
+SCOREBOARD_VERSION = 1
+BOARD_MAX_MEMBERS = 64
+BOARD_MAX_LOOKBACK = 128
+BOARD_HEADER_BYTES = 32
+BOARD_MEMBER_BYTES = 128
+SCOREBOARD_EXPORTS = ("sacenv_board_bytes", "sacenv_board_init", "sacenv_board_update", "sacenv_board_rewind")
+
+
+class Board(C.Structure):
+    """SacenvBoard (sacenv_scoreboard.h)."""
+    _fields_ = [("members", _i32), ("envs_per_member", _i32), ("env_base", _i32), ("lookback", _i32),
+                ("cap", _i64), ("member_floats", _i64)]
+
+
+class BoardMember(C.Structure):
+    """SacenvBoardMember: one member's 128-B record in the board."""
+    _fields_ = [("episodes", _i64), ("saves", _i64), ("last_save_step", _i64), ("last_end_step", _i64),
+                ("last", _d), ("best", _d), ("avg", _d), ("saved_now", C.c_uint32), ("reserved", C.c_uint32),
+                ("terms", C.c_uint64 * 8)]
+
+
 _LIB = None
 
 
@@ -315,7 +339,7 @@ def load(path: str | None = None):
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
         f.restype, f.argtypes = res, args
-    ES, QP = C.POINTER(EpisodeScan), C.POINTER(SacParams)
+    ES, QP, BP = C.POINTER(EpisodeScan), C.POINTER(SacParams), C.POINTER(Board)
     optional = (   # the headers beside sacenv.h: (names, argtypes), absent from a library built before them
         (EPISODE_EXPORTS, ([ES, C.POINTER(_i64)], [ES, _p, _p, _p, _p, _i64, _p])),
         (POPULATION_EXPORTS, (
@@ -327,7 +351,8 @@ def load(path: str | None = None):
             [RP, _i32, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
             [RP, _i32, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p],
             [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])),
-        (NOISE_EXPORTS, ([_i32, C.POINTER(C.c_uint64), _i32, C.POINTER(NoiseDraw), _p],)))
+        (NOISE_EXPORTS, ([_i32, C.POINTER(C.c_uint64), _i32, C.POINTER(NoiseDraw), _p],)),
+        (SCOREBOARD_EXPORTS, ([BP, C.POINTER(_i64)], [BP, _p, _p], [BP, _p, _p, _p, _p, _p], [BP, _p, _p])))
     for names, argtypes in optional:
         assert len(names) == len(argtypes)
         for name, args in zip(names, argtypes):

@@ -109,6 +109,9 @@ class EpisodeLog:
         self.episodes = 0                      # drained so far, dropped ones included
         self.best_score = float("-inf")
         self.term_counts = np.zeros(len(self.term_names), np.int64)
+        # readers of the device log that keep a cursor into it (sacenv/scoreboard.py): ``drain``
+        # lets each consume what is there before it empties the log, and rewinds them after
+        self.watchers = []
 
     @property
     def step0(self) -> int:
@@ -166,13 +169,18 @@ class EpisodeLog:
         """Synchronise the stream, return the stored entries (a structured array with
         fields end_step, score, env, length, term; ``min(total, capacity)`` of them, in
         the order they ended) and empty the device log. ``dropped`` is set to the number
-        of episodes that did not fit since the last drain."""
+        of episodes that did not fit since the last drain. Watchers (a ``MemberScoreboard``) are
+        updated first and rewound after, so they miss nothing and read nothing twice."""
+        for w in self.watchers:
+            w.update()
         torch.cuda.current_stream(self.device).synchronize()
         total = int(self._total.item())
         n = min(total, self.capacity)
         raw = self.log[HEADER_BYTES: HEADER_BYTES + _lib.EPISODE_ENTRY_BYTES * n].cpu().numpy()
         out = raw.view(ENTRY_DTYPE)
         self._total.zero_()
+        for w in self.watchers:
+            w.rewind()
         self.dropped = max(total - self.capacity, 0)
         self.dropped_total += self.dropped
         self.episodes += total
