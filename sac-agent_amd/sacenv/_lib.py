@@ -368,6 +368,27 @@ def load(path: str | None = None):
     return lib
 
 
+def require(names, header: str, lib=None) -> list:
+    """The entry points ``names`` of ``lib`` (default: the loaded library), in order. They belong
+    to ``header``, one of the headers beside sacenv.h: a library built before it lacks them."""
+    lib = lib or load()
+    fns = [getattr(lib, n, None) for n in names]
+    if any(f is None for f in fns):
+        raise SacenvError(f"{lib._name} was built before {header}: rebuild with "
+                          "`python __graft_entry__.py build`")
+    return fns
+
+
+def cuda_device(device, who: str):
+    """``device`` (default: the current GPU) as a ``torch.device`` with its index filled in;
+    ``who`` has no CPU path and says so."""
+    import torch
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise SacenvError(f"{who} runs on a GPU (HIP); no CPU path")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+
 def check(rc: int) -> None:
     if rc != 0:
         msg = load().sacenv_error_string(rc).decode()
@@ -401,11 +422,9 @@ def sac_pop_layout(params: SacParams, members: int) -> SacPopLayout:
 
 
 def replay_pop_layout(params: ReplayParams, members: int) -> ReplayPopLayout:
-    lib = load()
-    if not hasattr(lib, "sacenv_replay_pop_layout"):
-        raise SacenvError("this libsacenv.so was built before sacenv_population_replay.h")
+    fn, = require(REPLAY_POP_EXPORTS[:1], "sacenv_population_replay.h")
     out = ReplayPopLayout()
-    check(lib.sacenv_replay_pop_layout(C.byref(params), int(members), C.byref(out)))
+    check(fn(C.byref(params), int(members), C.byref(out)))
     return out
 
 

@@ -61,11 +61,7 @@ class EpisodeLog:
     def __init__(self, env, capacity: int = 1 << 20, *, history: int = 1 << 16, step0: int = 0,
                  log_buffer: torch.Tensor | None = None):
         self.lib = _lib.load()
-        self._update = getattr(self.lib, _lib.EPISODE_EXPORTS[1], None)
-        self._scratch_bytes = getattr(self.lib, _lib.EPISODE_EXPORTS[0], None)
-        if self._update is None or self._scratch_bytes is None:
-            raise _lib.SacenvError(f"{_lib.LIB_PATH} has no episode log (built before sacenv_episodes.h): "
-                                   "rebuild with `python __graft_entry__.py build`")
+        self._scratch_bytes, self._update = _lib.require(_lib.EPISODE_EXPORTS, "sacenv_episodes.h", self.lib)
         self.env = env
         self.device = env.device
         self.num_envs, self.n_pad = int(env.num_envs), int(env.n_pad)

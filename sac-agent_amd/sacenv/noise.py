@@ -35,10 +35,8 @@ class PolicyNoise:
             if int(s) != s or not 0 <= int(s) <= _U64:
                 raise ValueError(f"a noise seed is an integer in [0, 2^64), got {s!r}")
         self.seeds = tuple(int(s) for s in seeds)
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.SacenvError("PolicyNoise runs on the GPU only (libsacenv noise kernel)")
-        self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        self.device = _lib.cuda_device(device, "PolicyNoise")
+        self._normal, = _lib.require(_lib.NOISE_EXPORTS, "sacenv_noise.h")
         self._seeds = (C.c_uint64 * P)(*self.seeds)
 
     def draw(self, requests) -> list:
@@ -48,9 +46,6 @@ class PolicyNoise:
         reqs = [tuple(r) + (1,) * (4 - len(r)) for r in requests]
         if not 1 <= len(reqs) <= _lib.NOISE_MAX_STREAMS:
             raise ValueError(f"one launch serves 1..{_lib.NOISE_MAX_STREAMS} draws, got {len(reqs)}")
-        lib = _lib.load()
-        if not hasattr(lib, "sacenv_noise_normal"):
-            raise _lib.SacenvError("this libsacenv.so was built before sacenv_noise.h")
         P, sizes = self.P, []
         for stream, call, n, calls in reqs:
             if not (0 <= int(stream) <= _U64 and 0 <= int(call) and int(call) + int(calls) - 1 <= _U64):
@@ -68,7 +63,7 @@ class PolicyNoise:
             out.append(t)
             off += size
         stream_h = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(lib.sacenv_noise_normal(P, self._seeds, len(reqs), desc, stream_h))
+        _lib.check(self._normal(P, self._seeds, len(reqs), desc, stream_h))
         return out
 
     def normal(self, stream: int, call: int, n: int, calls: int = 1) -> torch.Tensor:

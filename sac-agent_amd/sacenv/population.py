@@ -14,7 +14,6 @@ members in and out.
 """
 from __future__ import annotations
 
-import ctypes as C
 import dataclasses
 import os
 import random
@@ -23,9 +22,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .agent import AgentConfig, VecSAC, load_models, save_models
-from .noise import ACT, LEARN1, LEARN2, PolicyNoise
-from .sac_native import NativeSAC, _set_param
+from .agent import AgentConfig, load_models, save_models
+from .sac_native import NativeSAC, SlabNets, _SacCore
 
 _COMMON = ("batch_size", "layer1_size", "layer2_size", "max_size")
 
@@ -70,28 +68,13 @@ def _common_configs(configs) -> list:
     return cfgs
 
 
-class PopulationMember:
-    """Member m: the five ``nn.Module``s on views of its slab, as ``NativeSAC`` has them."""
-
-    NETS = NativeSAC.NETS
-    _views = NativeSAC._views
-    adam_state = NativeSAC.adam_state
-    state_dicts = NativeSAC.state_dicts
-    optimizer_state = NativeSAC.optimizer_state
+class PopulationMember(SlabNets):
+    """Member m: the five ``nn.Module``s on views of its slab, as ``NativeSAC`` has them; the step,
+    the act count and the noise seed are the population's."""
 
     def __init__(self, pop, m: int, cfg: AgentConfig, init_seed, build: bool):
-        self.population, self.index, self.cfg = pop, m, cfg
-        self.params, self.layout = pop.params, pop.layout
-        self.weights = pop.weights[m]
-        ref = VecSAC("cpu", cfg, obs_dim=pop.params.obs_dim, n_actions=1, max_action=pop.params.max_action,
-                     init_seed=init_seed, with_memory=False)
-        for i, name in enumerate(self.NETS):
-            mod = getattr(ref, name)
-            for pname, view in self._views(self.weights, self.layout.net[i], name).items():
-                if build:  # the reference's initial weights under init_seed (NativeSAC.__init__)
-                    view.copy_(mod.state_dict()[pname].reshape(view.shape))
-                _set_param(mod, pname, view)
-            setattr(self, name, mod.to(pop.device))
+        self.population, self.index = pop, m
+        super().__init__(pop.weights[m], pop.params, pop.layout, cfg, pop.device, init_seed, build)
 
     @property
     def adam_step(self) -> int:
@@ -107,10 +90,7 @@ class PopulationMember:
         return None if seeds is None else seeds[self.index]
 
     def load_optimizer_state(self, state: dict) -> None:
-        for n in self.NETS[:4]:
-            for which, views in self.adam_state(n).items():
-                for k, v in views.items():
-                    v.copy_(state[f"{n}.{which}.{k}"].reshape(v.shape))
+        super().load_optimizer_state(state)
         self.loaded_step = int(state["step"])  # the population commits it (one step for all members)
         self.loaded_act_calls = int(state["act_calls"]) if "act_calls" in state else None
 
@@ -121,27 +101,26 @@ class PopulationMember:
                 "tvn_parameter_modulation_tau": c.tau}
 
 
-class NativeSACPopulation:
-    """P ``NativeSAC`` agents learning in lockstep, in one set of launches."""
+class NativeSACPopulation(_SacCore):
+    """P ``NativeSAC`` agents learning in lockstep, in one set of launches: ``_SacCore`` with
+    ``lead = (P,)``. ``choose_action``: [P, n, obs_dim] -> [P, n, 1]; ``learn`` takes stacked
+    batches (state [P, B, D], ...) or samples each member's own buffer -- P ``DeviceReplayBuffer``s,
+    or a ``PopulationReplay`` given as ``replay=`` (two launches, no stacking) -- and returns
+    [P, 4] losses."""
 
     def __init__(self, device, configs, *, obs_dim: int = 11, max_action: float = 1.0, init_seeds=None,
                  buffer_seeds=None, with_memory: bool = True, adam_eps: float = 1e-8, replay=None,
                  noise_seeds=None, _build: bool = True):
-        cfgs = _common_configs(configs)
+        cfgs = self.configs = _common_configs(configs)
         P = self.P = len(cfgs)
         cfg = cfgs[0]
-        if cfg.layer1_size != _lib.SAC_HIDDEN or cfg.layer2_size != _lib.SAC_HIDDEN:
-            raise ValueError(f"the SAC kernels are built for {_lib.SAC_HIDDEN}-wide layers")
         if P > _lib.POPULATION_MAX_MEMBERS:
             raise ValueError(f"a population holds at most {_lib.POPULATION_MAX_MEMBERS} members, got {P}")
         for name, seeds in (("init_seeds", init_seeds), ("buffer_seeds", buffer_seeds),
                             ("noise_seeds", noise_seeds)):
             if seeds is not None and len(seeds) != P:
                 raise ValueError(f"{name} must hold one seed per member")
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.SacenvError("NativeSACPopulation runs on the GPU only (libsacenv SAC kernels)")
-        self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        device = _lib.cuda_device(device, "NativeSACPopulation")
         if replay is not None:
             # one PopulationReplay for all members (sacenv/population_replay.py): checked before
             # anything is built or launched
@@ -150,33 +129,17 @@ class NativeSACPopulation:
                 raise TypeError("replay must be a PopulationReplay")
             for what, have, want in (("members", replay.P, P), ("max_size", replay.mem_size, cfg.max_size),
                                      ("obs_dim", replay.params.obs_dim, obs_dim), ("n_actions", replay.n_actions, 1),
-                                     ("device", replay.device, self.device)):
+                                     ("device", replay.device, device)):
                 if have != want:
                     raise ValueError(f"the replay's {what} ({have}) must be the population's ({want})")
-        self.configs = cfgs
-        # the fields the members share; lr_*, gamma, tau and reward_scale here are member 0's and
-        # are not read by the population entry points (they take self._hp)
-        self.params = _lib.SacParams(
-            obs_dim=obs_dim, n_actions=1, hidden=_lib.SAC_HIDDEN, batch=cfg.batch_size,
-            max_action=float(max_action), gamma=cfg.gamma, tau=cfg.tau, reward_scale=cfg.reward_scale,
-            lr_actor=cfg.lr_alpha, lr_critic=cfg.lr_beta, adam_beta1=0.9, adam_beta2=0.999,
-            adam_eps=float(adam_eps))
+        self._sync, self._act, self._learn = _lib.require(_lib.POPULATION_EXPORTS[1:], "sacenv_population.h")
+        # one member's noise is what a NativeSAC(noise_seed=noise_seeds[m]) draws
+        self.noise_seeds = None if noise_seeds is None else tuple(int(s) for s in noise_seeds)
+        super().__init__((P,), cfg, device, obs_dim, 1, max_action, adam_eps, self.noise_seeds)
         self._hp = (_lib.SacMember * P)(*[
             _lib.SacMember(lr_actor=c.lr_alpha, lr_critic=c.lr_beta, gamma=c.gamma, tau=c.tau,
                            reward_scale=c.reward_scale) for c in cfgs])
-        self.layout = _lib.sac_layout(self.params)          # inside a member's slab
-        PL = self.pop_layout = _lib.sac_pop_layout(self.params, P)
-        self.weights = torch.zeros((P, PL.member_floats), dtype=torch.float32, device=self.device)
-        self.scratch = torch.empty(PL.total_scratch_bytes // 4, dtype=torch.float32, device=self.device)
-        self.losses = torch.zeros((P, 4), dtype=torch.float32, device=self.device)
-        self.adam_step = 0
-        # counter-based policy noise (sacenv/noise.py), one seed per member: member m draws what a
-        # NativeSAC(noise_seed=noise_seeds[m]) draws; one act_calls for all, as one adam_step
-        self.noise_seeds = None if noise_seeds is None else tuple(int(s) for s in noise_seeds)
-        self.noise = None
-        if noise_seeds is not None:
-            self.noise = PolicyNoise(self.noise_seeds, self.device)
-        self.act_calls = 0
+        self._head, self._learn_head = (self._pp, P), (self._pp, P, self._hp)
         self.members = [PopulationMember(self, m, cfgs[m], None if init_seeds is None else init_seeds[m], _build)
                         for m in range(P)]
         if _build:
@@ -194,64 +157,9 @@ class NativeSACPopulation:
     def __len__(self) -> int:
         return self.P
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _native(self):
-        lib = _lib.load()
-        if not hasattr(lib, "sacenv_sac_pop_learn"):
-            raise _lib.SacenvError("this libsacenv.so was built before sacenv_population.h")
-        return lib
-
-    def sync(self) -> None:
-        """Refresh every member's kernel copies of the 256x256 layers after a host write."""
-        _lib.check(self._native().sacenv_sac_pop_sync(C.byref(self.params), self.P, self.weights.data_ptr(),
-                                                   self._stream()))
-
-    def _f32(self, x, n, what):
-        """f32, contiguous, on the device; ``n`` values with the member axis first."""
-        t = torch.as_tensor(x, device=self.device).to(torch.float32).contiguous()
-        if t.numel() != n or t.shape[0] != self.P:
-            raise ValueError(f"{what} must hold {n} values as [{self.P}, ...], got {list(t.shape)}")
-        return t
-
-    @torch.no_grad()
-    def choose_action(self, obs, eps=None):
-        """[P, n, obs_dim] -> [P, n, 1]: member m acts on its own n rows, one launch."""
-        obs = torch.as_tensor(obs, device=self.device).to(torch.float32).contiguous()
-        D = self.params.obs_dim
-        if obs.dim() != 3 or obs.shape[0] != self.P or obs.shape[2] != D:
-            raise ValueError(f"obs must be [{self.P}, n, {D}], got {list(obs.shape)}")
-        n = obs.shape[1]
-        if eps is not None:
-            eps = self._f32(eps, self.P * n, "eps")
-        elif self.noise is not None:
-            eps = self.noise.normal(ACT, self.act_calls, n)[0]
-        else:
-            eps = torch.randn((self.P, n), device=self.device)
-        out = torch.empty((self.P, n, 1), dtype=torch.float32, device=self.device)
-        _lib.check(self._native().sacenv_sac_pop_act(C.byref(self.params), self.P, self.weights.data_ptr(),
-                                                  obs.data_ptr(), n, eps.data_ptr(), out.data_ptr(), None,
-                                                  self._stream()))
-        self.act_calls += 1  # every accepted call is one act, wherever its eps came from
-        return out
-
-    def noise_for_step(self, n: int):
-        """``(eps [P, n], (e1, e2) [P, B] each)``: what the next ``choose_action`` on n rows per
-        member and the next ``learn`` would draw, from one launch; changes no state."""
-        if self.noise is None:
-            raise RuntimeError("noise_for_step needs a population built with noise_seeds")
-        B = self.configs[0].batch_size
-        eps, e1, e2 = self.noise.draw([(ACT, self.act_calls, n), (LEARN1, self.adam_step, B),
-                                       (LEARN2, self.adam_step, B)])
-        return eps[0], (e1[0], e2[0])
-
-    def act_noise(self, K: int, n: int) -> torch.Tensor:
-        """f32 [K, P, n]: row k is what the k-th ``choose_action`` from now would draw; changes
-        no state."""
-        if self.noise is None:
-            raise RuntimeError("act_noise needs a population built with noise_seeds")
-        return self.noise.normal(ACT, self.act_calls, n, calls=K)
+    def _sizes(self):
+        PL = self.pop_layout = _lib.sac_pop_layout(self.params, self.P)   # (self.layout: inside a member's slab)
+        return PL.member_floats, PL.total_scratch_bytes
 
     def remember(self, m: int, state, action, reward, new_state, code, **kw) -> None:
         """``memory[m].store_batch``: member m's transitions. (With a ``PopulationReplay`` the
@@ -266,61 +174,28 @@ class NativeSACPopulation:
     def sample(self):
         """One batch per member from its own buffer, as ``learn`` takes them: stacked, or with a
         ``PopulationReplay`` as its two launches write them."""
-        B = self.configs[0].batch_size
         if self._pop_replay:
-            return self.memory.sample(B, as_bool=False)[:5]
-        rows = [mem.sample(B, as_bool=False)[:5] for mem in self.memory]
+            return self.memory.sample(self._B, as_bool=False)[:5]
+        rows = [mem.sample(self._B, as_bool=False)[:5] for mem in self.memory]
         return tuple(torch.stack([r[k] for r in rows]) for k in range(5))
 
-    @torch.no_grad()
-    def learn(self, batch=None, noise=None, *, losses: bool = True):
-        """``NativeSAC.learn`` for every member. ``batch`` = stacked (state [P, B, D], action
-        [P, B, 1], reward [P, B], new_state, done); else each member's own buffer is sampled
-        (None until every buffer holds B rows; a ``PopulationReplay`` given as ``replay=`` is
-        sampled in two launches, with no stacking). ``noise`` = (eps1, eps2), each [P, B(, 1)].
-        Returns a [P, 4] tensor of (value, actor, critic 1, critic 2) losses: a copy, or with
-        ``losses=False`` the population's own buffer, which the next learn() rewrites."""
-        P, B, D = self.P, self.configs[0].batch_size, self.params.obs_dim
-        if batch is None:
-            if self.memory is None:
-                return None
-            if self.memory.mem_cntr < B if self._pop_replay else any(mem.mem_cntr < B for mem in self.memory):
-                return None
-            batch = self.sample()
-        state, action, reward, state_, done = batch
-        state = self._f32(state, P * B * D, "state")
-        state_ = self._f32(state_, P * B * D, "new_state")
-        action = self._f32(action, P * B, "action")
-        reward = torch.as_tensor(reward, device=self.device).to(torch.float64).contiguous()
-        done = torch.as_tensor(done, device=self.device).to(torch.uint8).contiguous()
-        if reward.numel() != P * B or reward.shape[0] != P or done.numel() != P * B or done.shape[0] != P:
-            raise ValueError(f"reward and done must be [{P}, {B}], got {list(reward.shape)} and {list(done.shape)}")
-        if noise is not None:
-            e1, e2 = self._f32(noise[0], P * B, "noise[0]"), self._f32(noise[1], P * B, "noise[1]")
-        elif self.noise is not None:
-            e1, e2 = (t[0] for t in self.noise.draw([(LEARN1, self.adam_step, B), (LEARN2, self.adam_step, B)]))
-        else:
-            e1, e2 = torch.randn((P, B), device=self.device), torch.randn((P, B), device=self.device)
-        step = self.adam_step + 1  # committed only once the call is accepted
-        _lib.check(self._native().sacenv_sac_pop_learn(
-            C.byref(self.params), P, self._hp, self.weights.data_ptr(), self.scratch.data_ptr(),
-            state.data_ptr(), action.data_ptr(), reward.data_ptr(), state_.data_ptr(), done.data_ptr(),
-            e1.data_ptr(), e2.data_ptr(), step, self.losses.data_ptr(), self._stream()))
-        self.adam_step = step
-        return self.losses.clone() if losses else self.losses
+    def _sample(self):
+        """``sample()`` once every member's buffer holds B rows."""
+        mem, B = self.memory, self._B
+        if mem is None or (mem.mem_cntr < B if self._pop_replay else any(b.mem_cntr < B for b in mem)):
+            return None
+        return self.sample()
 
     # ---- members in and out
 
     def export_member(self, m: int) -> NativeSAC:
         """A stand-alone ``NativeSAC`` with member m's weights, Adam moments, step, noise seed and
         act count (a copy)."""
-        agent = NativeSAC(self.device, self.configs[m], obs_dim=self.params.obs_dim,
-                          max_action=self.params.max_action, with_memory=False, adam_eps=self.params.adam_eps,
-                          noise_seed=None if self.noise_seeds is None else self.noise_seeds[m])
-        agent.weights.copy_(self.weights[m, : agent.weights.numel()])
-        agent.adam_step = self.adam_step
-        agent.act_calls = self.act_calls
-        return agent
+        p = self.params
+        return NativeSAC.from_slab(self.device, self.configs[m], self.weights[m], obs_dim=p.obs_dim,
+                                   max_action=p.max_action, adam_eps=p.adam_eps,
+                                   noise_seed=self.members[m].noise_seed, adam_step=self.adam_step,
+                                   act_calls=self.act_calls)
 
     @classmethod
     def from_agents(cls, agents, *, with_memory: bool = False, buffer_seeds=None) -> "NativeSACPopulation":

@@ -25,8 +25,7 @@ from .replay import TERMINAL_GOAL, DeviceReplayBuffer, _cuda_device, _ReplayAren
 class PopulationReplay(_ReplayArena):
     def __init__(self, members: int, max_size: int, input_shape, n_actions: int, *, device=None, seeds=None,
                  reward_f32: bool = True, terminal_mask: int = TERMINAL_GOAL):
-        if not hasattr(_lib.load(), "sacenv_replay_pop_store"):
-            raise _lib.SacenvError("this libsacenv.so was built before sacenv_population_replay.h")
+        _lib.require(_lib.REPLAY_POP_EXPORTS, "sacenv_population_replay.h")
         device = _cuda_device(device, "PopulationReplay")   # (a CPU device is refused before the members are looked at)
         P = self.P = int(members)
         if not 1 <= P <= _lib.REPLAY_POP_MAX_MEMBERS:

@@ -30,11 +30,7 @@ from . import _lib
 TERMINAL_GOAL = 1 << 1   # terminal = (code == 1): env term reached_goal, or a 0/1 done array
 
 
-def _cuda_device(device, who: str) -> torch.device:
-    dev = torch.device(device if device is not None else "cuda")
-    if dev.type != "cuda":
-        raise RuntimeError(f"{who} runs on a GPU (HIP); no CPU path")
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+_cuda_device = _lib.cuda_device
 
 
 def _replay_params(mem_size: int, obs_dim: int, act_dim: int, reward_f32=True,

@@ -27,14 +27,13 @@ from __future__ import annotations
 import csv
 import ctypes as C
 import os
-import types
 
 import numpy as np
 import torch
 
 from . import _lib
 from .agent import save_models
-from .sac_native import NativeSAC
+from .sac_native import NativeSAC, SlabNets
 
 # one member's record (SacenvBoardMember)
 MEMBER_DTYPE = np.dtype({
@@ -55,11 +54,8 @@ class MemberScoreboard:
 
     def __init__(self, log, members: int, envs_per_member: int, lookback: int = 50, population=None):
         self.lib = _lib.load()
-        fns = [getattr(self.lib, n, None) for n in _lib.SCOREBOARD_EXPORTS]
-        if any(f is None for f in fns):
-            raise _lib.SacenvError(f"{_lib.LIB_PATH} has no scoreboard (built before sacenv_scoreboard.h): "
-                                   "rebuild with `python __graft_entry__.py build`")
-        self._bytes, self._init, self._update, self._rewind = fns
+        self._bytes, self._init, self._update, self._rewind = _lib.require(
+            _lib.SCOREBOARD_EXPORTS, "sacenv_scoreboard.h", self.lib)
         self.log, self.population = log, population
         self.device = log.device
         self.P, self.N, self.L = int(members), int(envs_per_member), int(lookback)
@@ -162,21 +158,16 @@ class MemberScoreboard:
         """A stand-alone ``NativeSAC`` with the weights member m had at its last save (a copy, as
         ``NativeSACPopulation.export_member`` makes of the live ones)."""
         self._saved(m)
-        pop = self.population
-        agent = NativeSAC(self.device, pop.configs[m], obs_dim=pop.params.obs_dim, max_action=pop.params.max_action,
-                          with_memory=False, adam_eps=pop.params.adam_eps,
-                          noise_seed=None if pop.noise_seeds is None else pop.noise_seeds[m])
-        agent.weights.copy_(self.snapshot[m, : agent.weights.numel()])
-        return agent
+        pop, p = self.population, self.population.params
+        return NativeSAC.from_slab(self.device, pop.configs[m], self.snapshot[m], obs_dim=p.obs_dim,
+                                   max_action=p.max_action, adam_eps=p.adam_eps,
+                                   noise_seed=pop.members[m].noise_seed)
 
     def _view(self, m: int):
-        """Member m's five modules on views of its snapshot slab (a ``PopulationMember``)."""
+        """Member m's five modules on views of its snapshot slab (``SlabNets``; kept)."""
         if m not in self._views:
-            from .population import PopulationMember
             pop = self.population
-            shell = types.SimpleNamespace(weights=self.snapshot, params=pop.params, layout=pop.layout,
-                                          device=pop.device, adam_step=0, act_calls=0, noise_seeds=None)
-            self._views[m] = PopulationMember(shell, m, pop.configs[m], None, False)
+            self._views[m] = SlabNets(self.snapshot[m], pop.params, pop.layout, pop.configs[m], pop.device, None, False)
         return self._views[m]
 
     def save_models(self, experiment_dir: str) -> list:

@@ -61,11 +61,7 @@ class VecBoatEnv:
         self.num_envs = N = int(num_envs)
         if N <= 0:
             raise ValueError("num_envs must be positive")
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("VecBoatEnv runs on a GPU (HIP); no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _lib.cuda_device(device, "VecBoatEnv")
         self.env_id_offset = int(env_id_offset)
         self.autoreset = bool(autoreset)
         self.auto_refill = bool(auto_refill)

@@ -220,3 +220,94 @@ def test_native_learn_returns_independent_losses(gpu, built_lib):
     l2 = nat.learn(b2, n2)
     torch.cuda.synchronize()
     assert [float(x) for x in l1] == keep and [float(x) for x in l2] != keep
+
+
+def _cfg256():
+    from sacenv.agent import AgentConfig
+    return AgentConfig(batch_size=256, max_size=1 << 12)
+
+
+def generators_after(gpu, k, construct):
+    """((CPU state, device state) of torch's generators after ``manual_seed(k)`` and
+    ``construct()``, what ``construct`` returned)."""
+    torch.manual_seed(k)
+    made = construct()
+    return (torch.get_rng_state(), torch.cuda.get_rng_state(gpu)), made
+
+
+def check_generators(gpu, k, construct, cfgs, init_seeds=None, obs_dim=11):
+    """``construct()`` leaves both generators where one CPU ``VecSAC`` build per config leaves them,
+    in order, member i under ``init_seeds[i]``. An unseeded build draws from the global CPU generator
+    and leaves the device's alone. A seeded one runs under ``fork_rng(devices=[])``, which keeps the
+    CPU generator where it was -- and its ``torch.manual_seed(init_seed)`` seeds the device
+    generator too (``VecSAC.__init__``), which that fork does not restore. Returns what
+    ``construct`` made."""
+    from sacenv.agent import VecSAC
+
+    def builds():
+        for i, cfg in enumerate(cfgs):
+            VecSAC("cpu", cfg, obs_dim=obs_dim, n_actions=1, max_action=1.0,
+                   init_seed=None if init_seeds is None else init_seeds[i], with_memory=False)
+
+    got, made = generators_after(gpu, k, construct)
+    want, _ = generators_after(gpu, k, builds)
+    start, _ = generators_after(gpu, k, lambda: None)
+    assert torch.equal(got[0], want[0]), "the CPU generator"
+    assert torch.equal(got[1], want[1]), "the device generator"
+    if init_seeds is None:
+        assert torch.equal(got[1], start[1]) and (not cfgs) == torch.equal(got[0], start[0])
+    else:
+        assert torch.equal(got[0], start[0])
+    return made
+
+
+@pytest.mark.parametrize("init_seed", [None, 3])
+def test_native_construction_leaves_the_generators_as_before(gpu, built_lib, init_seed):
+    """Unseeded, the nets come from torch's global CPU generator (one ``VecSAC`` build); seeded,
+    they are built under ``fork_rng`` and the CPU state does not move (``check_generators``)."""
+    from sacenv.sac_native import NativeSAC
+    cfg = _cfg256()
+    for memory in (False, True):
+        check_generators(gpu, 21, lambda: NativeSAC(gpu, cfg, init_seed=init_seed, with_memory=memory, noise_seed=5),
+                         [cfg], None if init_seed is None else [init_seed])
+
+
+def _bits(agent):
+    torch.cuda.synchronize()
+    return agent.adam_step, agent.act_calls, agent.weights.clone(), agent.losses.view(torch.int32).clone()
+
+
+def same_bits(a, b):
+    return a[:2] == b[:2] and torch.equal(a[2], b[2]) and torch.equal(a[3], b[3])
+
+
+def test_native_refused_calls_change_nothing(gpu, built_lib):
+    """The ``ValueError`` cases of ``test_native_rejects_bad_shapes`` are host-side refusals: the
+    step, the act count, the weights and the losses stay bit for bit, and the next good ``learn``
+    is the one of an agent that never saw them."""
+    from sacenv.sac_native import NativeSAC
+    cfg = _cfg256()
+    nat, twin = (NativeSAC(gpu, cfg, init_seed=0, with_memory=False) for _ in range(2))
+    batch, noise = _batch(gpu, B=256, seed=3)
+    for agent in (nat, twin):       # one accepted act and learn first: non-trivial counters, moments and losses
+        agent.choose_action(batch[0][:65], eps=noise[0][:65])
+        agent.learn(batch, noise, losses=False)
+    before = _bits(nat)
+    assert before[:2] == (1, 1)
+    big, big_noise = _batch(gpu, B=512, seed=4)
+    bad = [lambda: nat.choose_action(torch.zeros((4, 10), device=gpu)),
+           lambda: nat.choose_action(batch[0][:4], eps=noise[0][:5]),
+           lambda: nat.learn(big, big_noise),
+           lambda: nat.learn(batch, big_noise)]
+    for k in range(5):
+        cut = list(batch)
+        cut[k] = cut[k][:1]
+        bad.append(lambda cut=tuple(cut): nat.learn(cut, noise))
+    for i, call in enumerate(bad):
+        with pytest.raises(ValueError):
+            call()
+        assert same_bits(_bits(nat), before), i
+    batch, noise = _batch(gpu, B=256, seed=5)
+    nat.learn(batch, noise, losses=False)
+    twin.learn(batch, noise, losses=False)
+    assert _bits(nat)[:2] == (2, 1) and same_bits(_bits(nat), _bits(twin))

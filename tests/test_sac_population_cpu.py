@@ -66,6 +66,27 @@ def test_lib_loads_a_library_without_the_population_entry_points(built_lib, tmp_
     lib = _lib.load(str(so))
     assert lib.sacenv_abi_version() == _lib.ABI_VERSION
     assert not any(hasattr(lib, n) for n in _lib.POPULATION_EXPORTS)
+    # what needs them says which header the library is older than; what the library has is handed out
+    with pytest.raises(_lib.SacenvError, match=r"sacenv_population\.h"):
+        _lib.require(_lib.POPULATION_EXPORTS, "sacenv_population.h", lib)
+    with pytest.raises(_lib.SacenvError, match=r"sacenv_noise\.h"):
+        _lib.require(("sacenv_sac_act",) + _lib.NOISE_EXPORTS, "sacenv_noise.h", lib)
+    assert [f.__name__ for f in _lib.require(("sacenv_sac_act", "sacenv_sac_learn"), "sacenv.h", lib)] == \
+        ["sacenv_sac_act", "sacenv_sac_learn"]
+    assert [f.__name__ for f in _lib.require(_lib.POPULATION_EXPORTS, "sacenv_population.h")] == \
+        list(_lib.POPULATION_EXPORTS)
+
+
+def test_cuda_device_refuses_the_cpu_and_names_the_caller():
+    import torch
+    from sacenv import _lib
+    assert issubclass(_lib.SacenvError, RuntimeError)
+    for dev in ("cpu", torch.device("cpu")):
+        with pytest.raises(_lib.SacenvError, match="X runs on a GPU"):
+            _lib.cuda_device(dev, "X")
+    assert _lib.cuda_device("cuda:1", "X") == torch.device("cuda", 1)      # an index given is kept, no device asked
+    from sacenv.replay import _cuda_device
+    assert _cuda_device is _lib.cuda_device
 
 
 def test_population_structs_match_c_layout(tmp_path):

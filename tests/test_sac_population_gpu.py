@@ -218,6 +218,28 @@ def test_export_member_and_from_agents_round_trip(gpu, built_lib):
     other = _agents(gpu, 1, 512, D)[0]
     with pytest.raises(ValueError):
         NativeSACPopulation.from_agents([agents[0], other])
+    # out and in again, with noise seeds and an act count: weights, step, act count and seeds come back
+    for P in (1, 3):
+        seeds = tuple(2 ** 63 + 5 - m for m in range(P))
+        pop = _population(gpu, P, B, D, noise_seeds=seeds)
+        per, batch, noise = _stacked(gpu, P, B, D, 5)
+        pop.choose_action(batch[0][:, :65])
+        pop.learn(batch, noise, losses=False)
+        copies = [pop.export_member(m) for m in range(P)]
+        for m, c in enumerate(copies):
+            assert (c.adam_step, c.act_calls, c.noise_seed, c.memory) == (1, 1, seeds[m], None)
+            assert c.cfg == pop.configs[m] and c.params.adam_eps == pop.params.adam_eps
+            assert c.weights.data_ptr() != pop.weights[m].data_ptr() and torch.equal(c.weights, pop.weights[m])
+        back = NativeSACPopulation.from_agents(copies)
+        assert (back.adam_step, back.act_calls, back.noise_seeds, back.configs) == (1, 1, seeds, pop.configs)
+        assert torch.equal(back.weights, pop.weights)
+        obs = batch[0][:, :63]
+        assert torch.equal(back.choose_action(obs), pop.choose_action(obs))      # the seeded draw of act 1
+        _, batch, _ = _stacked(gpu, P, B, D, 6)
+        back.learn(batch, losses=False)                                         # and of step 1
+        pop.learn(batch, losses=False)
+        torch.cuda.synchronize()
+        assert torch.equal(back.weights, pop.weights) and torch.equal(back.losses, pop.losses)
 
 
 @pytest.mark.parametrize("optimizer", [False, True])
@@ -333,3 +355,59 @@ def test_bad_shapes_raise_before_any_launch(gpu, built_lib):
     torch.cuda.synchronize()
     assert pop.adam_step == 0 and torch.equal(pop.weights, w0)
     assert dataclasses.is_dataclass(pop.configs[0])
+
+
+def test_refused_calls_change_nothing(gpu, built_lib):
+    """Every ``ValueError`` case of ``test_bad_shapes_raise_before_any_launch`` is a host-side
+    refusal: the step, the act count, the weights and the losses stay bit for bit, and the next good
+    ``learn`` is the one of a population that never saw them."""
+    from sacenv import _lib
+    from test_sac_native_gpu import _bits, same_bits
+    P, B, D = 2, 256, 11
+    pop, twin = (_population(gpu, P, B, D) for _ in range(2))
+    _, batch, noise = _stacked(gpu, P, B, D, 1)
+    _, batch3, noise3 = _stacked(gpu, 3, B, D, 1)
+    for p in (pop, twin):           # one accepted act and learn first: non-trivial counters, moments and losses
+        p.choose_action(batch[0][:, :65], noise[0][:, :65])
+        p.learn(batch, noise, losses=False)
+    before = _bits(pop)
+    assert before[:2] == (1, 1)
+    bad = [lambda: pop.learn(batch3, noise3), lambda: pop.learn(batch, noise3),
+           lambda: pop.learn(tuple(t[:, : B // 2] for t in batch), noise),
+           lambda: pop.choose_action(batch3[0]), lambda: pop.choose_action(batch[0][0]),
+           lambda: pop.choose_action(batch[0], noise3[0]),
+           lambda: _population(gpu, _lib.POPULATION_MAX_MEMBERS + 1, B, D)]
+    for k in range(5):
+        cut = list(batch)
+        cut[k] = cut[k][:1]
+        bad.append(lambda cut=tuple(cut): pop.learn(cut, noise))
+    for i, call in enumerate(bad):
+        with pytest.raises(ValueError):
+            call()
+        assert same_bits(_bits(pop), before), i
+    _, batch, noise = _stacked(gpu, P, B, D, 2)
+    pop.learn(batch, noise, losses=False)
+    twin.learn(batch, noise, losses=False)
+    assert _bits(pop)[:2] == (2, 1) and same_bits(_bits(pop), _bits(twin))
+
+
+@pytest.mark.parametrize("path", ["unseeded", "seeded", "from_agents", "export_member"])
+def test_construction_leaves_the_generators_as_before(gpu, built_lib, path):
+    """Per constructing path, the CPU net builds it makes (``from_agents`` and ``export_member``
+    build unseeded nets they then overwrite) leave torch's generators as those builds alone do
+    (tests/test_sac_native_gpu.py: ``check_generators``)."""
+    from sacenv.population import NativeSACPopulation
+    from test_sac_native_gpu import check_generators
+    P, B, D = 2, 256, 11
+    cfgs = [_cfg(m, B) for m in range(P)]
+    if path in ("unseeded", "seeded"):
+        seeds = [10, 11] if path == "seeded" else None
+        made = check_generators(gpu, 31, lambda: NativeSACPopulation(gpu, cfgs, obs_dim=D, init_seeds=seeds,
+                                                                     noise_seeds=[3, 4]), cfgs, seeds, D)
+    elif path == "from_agents":
+        agents = _agents(gpu, P, B, D, noise_seed=3)
+        made = check_generators(gpu, 31, lambda: NativeSACPopulation.from_agents(agents), cfgs, None, D)
+    else:
+        pop = _population(gpu, P, B, D, noise_seeds=[3, 4])
+        made = check_generators(gpu, 31, lambda: pop.export_member(1), cfgs[1:], None, D)
+    assert made is not None

@@ -434,3 +434,81 @@ def test_the_example_keeps_the_best(gpu, built_lib, tmp_path, monkeypatch, capsy
     assert not {"device_table", "kept", "best_member"} & set(plain) and set(plain) | {"device_table", "kept",
                                                                                       "best_member"} == set(out)
     assert set(plain["table"][0]) == set(out["table"][0]) - {"saves", "last_save_step"}
+
+
+def _board_where_all_saved(gpu, built_lib):
+    """A ``MemberScoreboard`` over a fresh population of three members, fed the entries of
+    ``_three_calls`` through a log buffer written by hand (no env): every member saved its initial
+    weights. Then one ``learn``: the live weights have moved on."""
+    import types
+    from sacenv import MemberScoreboard
+    from test_sac_population_gpu import _population, _stacked
+    P = 3
+    pop = _population(gpu, P, 256, 11, noise_seeds=[5, 6, 7])
+    dev = Dev(gpu, built_lib, P, 64, 5, cap=64)
+    log = types.SimpleNamespace(device=gpu, env_base=0, capacity=64, watchers=[], log=dev.log, term_names=())
+    board = MemberScoreboard(log, P, 64, lookback=5, population=pop)
+    at = 0
+    for call in _three_calls():
+        dev.write(at + len(call), call, at)
+        at += len(call)
+        board.update()
+    assert board.records()["saves"].tolist() == [1, 1, 1] and torch.equal(board.snapshot, pop.weights)
+    _, batch, noise = _stacked(gpu, P, 256, 11, 1)
+    pop.learn(batch, noise, losses=False)
+    return pop, board
+
+
+def test_saved_members_leave_the_generators_as_before(gpu, built_lib, tmp_path):
+    """``snapshot_member`` builds one set of nets from torch's global CPU generator (and overwrites
+    them), the first ``save_models`` one per member that saved, the second none: the views are
+    kept (tests/test_sac_native_gpu.py: ``check_generators``)."""
+    from test_sac_native_gpu import check_generators
+    pop, board = _board_where_all_saved(gpu, built_lib)
+    assert check_generators(gpu, 41, lambda: board.snapshot_member(1), pop.configs[1:2]) is not None
+    for builds in (pop.configs, []):
+        assert check_generators(gpu, 41, lambda: board.save_models(str(tmp_path)), builds) == [0, 1, 2]
+
+
+def test_member_views_sit_on_the_snapshot(gpu, built_lib, tmp_path, monkeypatch):
+    """The modules ``save_models`` writes from are ``SlabNets`` on ``board.snapshot[m]`` (no
+    population stands behind them); the files load into a fresh ``NativeSAC`` whose weights are
+    ``snapshot_member(m)``'s bit for bit; ``snapshot_member`` and ``export_member`` are both
+    ``NativeSAC.from_slab``."""
+    from sacenv.sac_native import NativeSAC, SlabNets
+    pop, board = _board_where_all_saved(gpu, built_lib)
+    calls = []
+    real = NativeSAC.from_slab.__func__
+    monkeypatch.setattr(NativeSAC, "from_slab",
+                        classmethod(lambda cls, *a, **kw: (calls.append(cls), real(cls, *a, **kw))[1]))
+    assert board.save_models(str(tmp_path)) == [0, 1, 2] and not calls
+    esz = board.snapshot.element_size()
+    off = pop.layout.net[2] + pop.layout.tensor[1][5]                   # critic_2's q.bias in a slab
+    for m in range(3):
+        snap, live = board.snapshot_member(m), pop.export_member(m)
+        assert calls == [NativeSAC] * (3 * m + 2)                       # (a third at the end of each round)
+        assert (snap.cfg, snap.noise_seed, snap.params.adam_eps) == (live.cfg, live.noise_seed, live.params.adam_eps)
+        assert (snap.adam_step, snap.act_calls, live.adam_step, live.act_calls) == (0, 0, 1, 0)
+        assert torch.equal(snap.weights, board.snapshot[m]) and torch.equal(live.weights, pop.weights[m])
+        assert not torch.equal(snap.weights, live.weights)
+        # the files: the snapshot's nets; a fresh agent has the snapshot's zero moments and, after
+        # load_models' sync, its kernel copies
+        loaded = NativeSAC(gpu, pop.configs[m], with_memory=False)
+        loaded.load_models(str(tmp_path / f"member_{m}"))
+        torch.cuda.synchronize(gpu)
+        assert torch.equal(loaded.weights, snap.weights), m
+        # the view: five modules whose parameters lie inside snapshot[m], and write through to it
+        view = board._view(m)
+        assert type(view) is SlabNets and board._view(m) is view and view.cfg == pop.configs[m]
+        lo = board.snapshot[m].data_ptr()
+        hi = lo + board.snapshot[m].numel() * esz
+        for net in view.NETS:
+            for p in getattr(view, net).parameters():
+                assert lo <= p.data_ptr() and p.data_ptr() + p.numel() * esz <= hi, (m, net)
+        assert view.critic_2.q.bias.data_ptr() == lo + off * esz
+        with torch.no_grad():
+            view.critic_2.q.bias.fill_(-3.5)
+        assert float(board.snapshot[m, off]) == -3.5 and float(pop.weights[m, off]) != -3.5
+        assert float(board.snapshot_member(m).weights[off]) == -3.5
+
+
