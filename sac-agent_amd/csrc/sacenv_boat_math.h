@@ -13,6 +13,13 @@
 
 namespace {
 
+// A wave-uniform test: does any active lane hold x? Where x is one compare with no
+// other use the compiler branches on the compare's own lane mask; where x has other
+// uses (the step's refresh predicate) it rebuilds the mask with a 0/1 select and a
+// second compare, and does so for __builtin_amdgcn_ballot_w64 too, alone or as the
+// scalar or of one ballot per compare (the same or one instruction more: DESIGN §4.1).
+__device__ __forceinline__ bool any_lane(bool x) { return __ballot(x) != 0ull; }
+
 // The polynomial coefficients below as loop-invariant VGPR copies (trig_k(),
 // once per launch). Written as plain fma() with literals, the compiler builds
 // each 64-bit coefficient with two v_mov_b32 and a v_fmac; read from SGPRs,
@@ -157,7 +164,7 @@ __device__ __forceinline__ SinCos sincos_ocml(double x) {
 __device__ __forceinline__ void sincos_cw(double x, double* sp, double* cp, const TrigK& K) {
   sincos_fast(x, sp, cp, K);
   const bool ok = fabs(x) <= kCwBound;
-  if (__builtin_expect(__ballot(!ok) != 0ull, 0)) {  // (unlikely: laid out off the step's fall-through path)
+  if (__builtin_expect(any_lane(!ok), 0)) {  // (unlikely: laid out off the step's fall-through path)
     if (!ok) {
       const SinCos r = sincos_ocml(x);
       *sp = r.s, *cp = r.c;
@@ -194,7 +201,7 @@ __device__ __forceinline__ void trig3(double j, double r, double w, double* sj, 
   *sr = fma(r * zr, qr, r);
   sincos_quadrant(rw, zw, ps, pc, kw, sw, cw);
   const bool okj = fabs(j) <= kSinBound, okr = fabs(r) <= kSinBound, okw = fabs(w) <= kCwBound;
-  if (__builtin_expect(__ballot(!(okj && okr && okw)) != 0ull, 0)) {
+  if (__builtin_expect(any_lane(!(okj && okr && okw)), 0)) {
     if (!okj) *sj = sin_ocml(j);
     if (!okr) *sr = sin_ocml(r);
     if (!okw) {

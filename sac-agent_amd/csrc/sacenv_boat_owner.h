@@ -409,6 +409,33 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   bool refresh = false, any_refresh = false;
   int jn = 0;
   double rq[kCoef];  // refreshed piece (refresh lanes), stored at the end
+  // autoreset: the next pre-drawn episode's curve values at grid index 0 and
+  // start y. Lanes in an episode's first step gather them from the slot ring
+  // and refresh their lane-coalesced copies; the others read the copies. The
+  // one-step launch: one unconditional load per value from a per-lane address
+  // (no divergent branch: see the refresh loads below; no select between two
+  // loaded registers either).
+  double y0n[2];
+  int32_t syn = 0;
+  const bool hdr_refresh = autoreset && index == 0;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) y0n[c] = y0c[c];
+  if (kRoll) syn = syc;
+  const auto hdr_gather = [&]() {
+    const int ns = nslot;  // (cons + 1) % kSlots
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+      if (c < nc) {
+        // (rollout: the copy is in registers; other lanes read the ring's first line)
+        const double v = *(hdr_refresh ? reinterpret_cast<const double*>(wbase + sno + (uint32_t)(c * A.nk) * 16u)
+                                       : (kRoll ? A.wind_knots() : &A.f64e(U_W0N + 8 * c, eo)));
+        y0n[c] = kRoll && !hdr_refresh ? y0c[c] : v;
+      }
+    if (nc == 0 && exp2) {
+      const int32_t v = *(hdr_refresh ? &A.i32e(U_STARTY + 4 * ns, eo4) : &A.i32e(U_SYN, eo4));
+      syn = kRoll && !hdr_refresh ? syc : v;
+    }
+  };
   if (nc == 0) {
     wind_at(p, A, T.table, 0, e, wi, wv, wa);  // constants or the shared table
   } else {
@@ -428,9 +455,18 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
     knext = knot_coord(p, wn);
     jn = knext.j;
     refresh = index == 0 || jn != kcur.j;
-    // (one wave-uniform branch: in ~3 of 4 steps no lane of the wave refreshes)
-    any_refresh = __builtin_expect(__ballot(refresh) != 0ull, 0);
-    if (any_refresh) {  // the piece of the next step's interval for refreshing lanes, stored at
+    // (one wave-uniform branch: in ~3 of 4 steps no lane of the wave refreshes. It is the
+    // multi-step loop's one rare-event test at the head of the step: its region, laid
+    // out behind the loop, holds the header gathers, behind a uniform test of their own
+    // -- a lane in its episode's first step is a refresh lane --, and the piece gathers.
+    // The hint is a probability, not "never": with the plain unlikely hint the
+    // register allocator spent 2-4 VGPRs more in some instantiations)
+    any_refresh = any_lane(refresh);
+    if (__builtin_expect_with_probability(any_refresh, 0, 0.9)) {
+      // (multi-step loop: the header copies are in registers, and only a step with a
+      // lane in its episode's first step -- the step after a restart -- gathers)
+      if (kRoll && any_lane(hdr_refresh)) hdr_gather();
+      // the piece of the next step's interval for refreshing lanes, stored at
       // the end (own registers, read only there). Unconditional loads, the
       // other lanes reading one fixed line: with no branch around them the
       // waitcnt pass can count the loads in flight (a load under a divergent
@@ -444,36 +480,9 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
         }
     }
   }
-  // autoreset: the next pre-drawn episode's curve values at grid index 0 and
-  // start y. Lanes in an episode's first step gather them from the slot ring
-  // and refresh their lane-coalesced copies; the others read the copies. The
-  // one-step launch: one unconditional load per value from a per-lane address
-  // (no divergent branch: see the refresh loads above; no select between two
-  // loaded registers either).
-  double y0n[2];
-  int32_t syn = 0;
-  const bool hdr_refresh = autoreset && index == 0;
-  // (multi-step loop: the copies are in registers, and only a step with a lane in
-  // its episode's first step -- the step after a restart -- gathers: one wave-uniform
-  // branch, off the common path, around the gathers)
-#pragma unroll
-  for (int c = 0; c < 2; ++c) y0n[c] = y0c[c];
-  if (kRoll) syn = syc;
-  if (!kRoll || __builtin_expect(__ballot(hdr_refresh) != 0ull, 0)) {
-    const int ns = nslot;  // (cons + 1) % kSlots
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-      if (c < nc) {
-        // (rollout: the copy is in registers; other lanes read the ring's first line)
-        const double v = *(hdr_refresh ? reinterpret_cast<const double*>(wbase + sno + (uint32_t)(c * A.nk) * 16u)
-                                       : (kRoll ? A.wind_knots() : &A.f64e(U_W0N + 8 * c, eo)));
-        y0n[c] = kRoll && !hdr_refresh ? y0c[c] : v;
-      }
-    if (nc == 0 && exp2) {
-      const int32_t v = *(hdr_refresh ? &A.i32e(U_STARTY + 4 * ns, eo4) : &A.i32e(U_SYN, eo4));
-      syn = kRoll && !hdr_refresh ? syc : v;
-    }
-  }
+  // (the one-step launch: unconditional; no curve: no refresh region, and the one
+  // header value, exp 2's start y, behind its own test)
+  if (!kRoll || (nc == 0 && exp2 && __builtin_expect(any_lane(hdr_refresh), 0))) hdr_gather();
   OWNER_STAMP(st_loaded);
   const double r_mx = T.r_mx, r_my = T.r_my, r_iz = T.r_iz, r_nd = T.r_nd, r_w = T.r_w;
 
@@ -486,7 +495,7 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   // and NaN / 10 = NaN, behind a wave-uniform branch that is almost never taken
   if (p.test_mode == 0) {
     double moved = rudder + div_c((double)act, 10.0, 0.1);
-    if (__builtin_expect(__ballot(!__builtin_isfinite(act)) != 0ull, 0)) {
+    if (__builtin_expect(any_lane(!__builtin_isfinite(act)), 0)) {
       if (!__builtin_isfinite(act)) moved = rudder + (double)act;
     }
     rudder = moved;
@@ -644,7 +653,7 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
   // through. (After the staged row's stores: a restarting lane's obs3_next
   // lands in the row just stored, and the later store wins.)
   // (the one-step launch: the restart's selects behind its own uniform branch, as before)
-  if (kRoll ? __builtin_expect(__ballot(ended) != 0ull, 0) : __ballot(restart) != 0ull) {
+  if (kRoll ? __builtin_expect(any_lane(ended), 0) : __ballot(restart) != 0ull) {
     if (kRoll) {
       if ((uint32_t)term - 1u < 5u)  // codes 1..5 (no-return atomic: nothing waits for it)
         __hip_atomic_fetch_add(&A.at_e<uint32_t>(U_CNT + 4 * (term - 1), eo4), 1u, __ATOMIC_RELAXED,
@@ -716,7 +725,11 @@ __device__ __forceinline__ void owner_wave(const SacenvBoatParams& pin, const Ar
       if (exp2) st_out(A.i32e(U_SYN, eo4), syn);
     }
   } else {  // the same updates, in registers (each behind a wave-uniform branch)
-    if (nc > 0 && any_refresh) {  // (the branch of the loads above)
+    // (the saved result of the step's head test: a cold block behind the loop with its
+    // register copies, no exec-mask skip on the fall-through path. One owner wave per
+    // SIMD only: with the hint a two-waves-per-SIMD instantiation, exp 4/5's staged
+    // rows, allocates a 20-B private segment it never touches)
+    if (nc > 0 && (kVc ? __builtin_expect(any_refresh, 0) : any_refresh)) {
       if (refresh && !restart) {
 #pragma unroll
         for (int k = 0; k < kCoef; ++k) cf[k] = rq[k];
