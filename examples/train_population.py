@@ -14,6 +14,7 @@ as OS processes, three at a time; here they are the members of one ``NativeSACPo
 
     python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
         [--replay population|members] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
+        [--select-every K [--quantile Q] [--min-episodes E] [--select-seed 0]]
 
 ``--noise counter`` gives member m the noise seed ``--noise-seed`` + m (``sacenv.PolicyNoise``): the
 act draw and both learn draws of an iteration come from one launch for all members, and member m's
@@ -30,6 +31,15 @@ an episode's score beats the look-back average (main.py:106-108). A ``MemberScor
 the episode log on the device, is updated after every ``learn`` and snapshots the weights of the
 members the rule selects; at the end its table is printed beside the post-hoc one, and the
 snapshots go to DIR/member_<m>/checkpoints/ with DIR/overview.csv (main.py:121-128).
+
+``--select-every K`` turns the search into population-based training: every K iterations a
+``PopulationSelection`` ranks the members by their look-back mean on the device and the worst
+``--quantile`` of those that finished ``--min-episodes`` episodes since their last replacement
+become copies of the best -- weights, Adam moments and all -- with the winner's four values, each
+times 0.8 or 1.2 and clipped to the search ranges. One line is printed per replacement, and the
+JSON line gains ``selection`` (per member: rank, times replaced, parent, current values) and
+``replacements``. The table's drawn values are then the members' LAST ones. Without the flag
+nothing changes.
 """
 from __future__ import annotations
 
@@ -63,6 +73,14 @@ def main(argv=None):
     ap.add_argument("--keep-best", default=None, metavar="DIR",
                     help="snapshot a member whenever an episode of its beats the look-back average; write the "
                          "snapshots and overview.csv to DIR")
+    ap.add_argument("--select-every", type=int, default=0, metavar="K",
+                    help="every K iterations the worst members copy the best (0: never)")
+    ap.add_argument("--quantile", type=int, default=None,
+                    help="how many members lose, and how many may be copied from (default: members // 4)")
+    ap.add_argument("--min-episodes", type=int, default=None,
+                    help="episodes a member finishes after a replacement before it is ranked again "
+                         "(default: --lookback)")
+    ap.add_argument("--select-seed", type=int, default=0, help="seed of the selection's draws")
     ap.add_argument("--max-episode-steps", type=int, default=500)
     args = ap.parse_args(argv)
     P, N = args.members, args.envs_per_member
@@ -85,16 +103,23 @@ def main(argv=None):
                      max_episode_steps=args.max_episode_steps)
     obs = env.reset().clone()
     log = EpisodeLog(env)
-    board = None
+    board = selection = scores = None
     if args.keep_best:
         from sacenv import MemberScoreboard
         board = MemberScoreboard(log, P, N, lookback=args.lookback, population=pop)
+    if args.select_every > 0:
+        from sacenv import MemberScoreboard, PopulationSelection
+        # the look-back means the selection ranks by: --keep-best's board, or one without a snapshot
+        scores = board if board is not None else MemberScoreboard(log, P, N, lookback=args.lookback)
+        selection = PopulationSelection(scores, pop, quantile=args.quantile, min_episodes=args.min_episodes,
+                                        seed=args.select_seed)
+    replacements = []
     # terminal as main.py:83-88 stores it: each env's last termination, kept per member
     last_term = [torch.zeros(N, dtype=torch.uint8, device=dev) for _ in range(P)]
     losses = None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.iters):
+    for it in range(args.iters):
         eps = noise = None
         if pop.noise is not None:  # the act draw and both learn draws of this iteration: one launch
             eps, noise = pop.noise_for_step(N)
@@ -112,6 +137,13 @@ def main(argv=None):
         losses = out if out is not None else losses
         if board is not None:  # after learn: where main.py:106 saves
             board.update()
+        if selection is not None and it % args.select_every == args.select_every - 1:
+            if scores is not board:
+                scores.update()
+            for r in selection.step():  # two launches, then the one read-back: the new values go to learn's table
+                replacements.append({"iter": it, **r})
+                print(f"iter {it}: member {r['member']} <- member {r['source']}: "
+                      + json.dumps(pop.members[r["member"]].hpset()))
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     entries = log.drain()  # (the board reads what is left first)
@@ -155,6 +187,8 @@ def main(argv=None):
            "losses": None if losses is None else losses.tolist(), "table": table}
     if board is not None:
         out.update(device_table=device_table, kept=kept, best_member=board.best_member())
+    if selection is not None:
+        out.update(selection=selection.table(), replacements=replacements)
     print(json.dumps(out))
     return out
 

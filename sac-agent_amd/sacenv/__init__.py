@@ -10,7 +10,7 @@ from .spaces import Box
 
 __all__ = ["BoatConfig", "Box", "VecBoatEnv", "BoatEnv", "ParachuteEnv", "CarEnv", "VecToyEnv",
            "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "PopulationReplay", "PolicyNoise",
-           "MemberScoreboard", "_lib"]
+           "MemberScoreboard", "PopulationSelection", "_lib"]
 
 
 def __getattr__(name):  # lazy: importing torch-dependent classes only when used
@@ -35,4 +35,7 @@ def __getattr__(name):  # lazy: importing torch-dependent classes only when used
     if name == "MemberScoreboard":
         from .scoreboard import MemberScoreboard
         return MemberScoreboard
+    if name == "PopulationSelection":
+        from .selection import PopulationSelection
+        return PopulationSelection
     raise AttributeError(name)

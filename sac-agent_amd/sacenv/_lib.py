@@ -245,6 +245,30 @@ class BoardMember(C.Structure):
                 ("terms", C.c_uint64 * 8)]
 
 
+# include/sacenv_selection.h (SACENV_SELECTION_VERSION 1): truncation selection on the board and
+# the population's slab; beside the ABI of sacenv.h, bound only where the library has them
+SELECTION_VERSION = 1
+SELECT_MAX_MEMBERS = 64
+SELECT_HEADER_BYTES = 32
+SELECT_MEMBER_BYTES = 64
+SELECT_KEY1 = 0x73656C656374
+SELECT_COPY_THREADS, SELECT_COPY_UNROLL, SELECT_COPY_CHUNKS = 256, 4, 256
+SELECTION_EXPORTS = ("sacenv_select_bytes", "sacenv_select_init", "sacenv_select_step")
+
+
+class Select(C.Structure):
+    """SacenvSelect (sacenv_selection.h)."""
+    _fields_ = [("members", _i32), ("quantile", _i32), ("lookback", _i32), ("reserved", _i32),
+                ("min_episodes", _i64), ("member_floats", _i64), ("seed", C.c_uint64),
+                ("factor", _d * 2), ("lo", _d * 4), ("hi", _d * 4)]
+
+
+class SelectMember(C.Structure):
+    """SacenvSelectMember: one member's 64-B record in the selection state."""
+    _fields_ = [("since", _i64), ("replaced", _i64), ("source_now", _i32), ("rank_now", _i32),
+                ("parent", _i32), ("reserved", _i32), ("hp", _d * 4)]
+
+
 _LIB = None
 
 
@@ -339,7 +363,7 @@ def load(path: str | None = None):
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
         f.restype, f.argtypes = res, args
-    ES, QP, BP = C.POINTER(EpisodeScan), C.POINTER(SacParams), C.POINTER(Board)
+    ES, QP, BP, XP = C.POINTER(EpisodeScan), C.POINTER(SacParams), C.POINTER(Board), C.POINTER(Select)
     optional = (   # the headers beside sacenv.h: (names, argtypes), absent from a library built before them
         (EPISODE_EXPORTS, ([ES, C.POINTER(_i64)], [ES, _p, _p, _p, _p, _i64, _p])),
         (POPULATION_EXPORTS, (
@@ -352,7 +376,8 @@ def load(path: str | None = None):
             [RP, _i32, _p, _i32, _i64, _p, _p, _p, _p, _p, _p, _p],
             [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])),
         (NOISE_EXPORTS, ([_i32, C.POINTER(C.c_uint64), _i32, C.POINTER(NoiseDraw), _p],)),
-        (SCOREBOARD_EXPORTS, ([BP, C.POINTER(_i64)], [BP, _p, _p], [BP, _p, _p, _p, _p, _p], [BP, _p, _p])))
+        (SCOREBOARD_EXPORTS, ([BP, C.POINTER(_i64)], [BP, _p, _p], [BP, _p, _p, _p, _p, _p], [BP, _p, _p])),
+        (SELECTION_EXPORTS, ([XP, C.POINTER(_i64)], [XP, C.POINTER(SacMember), _p, _p], [XP, _p, _p, _p, _p])))
     for names, argtypes in optional:
         assert len(names) == len(argtypes)
         for name, args in zip(names, argtypes):
