@@ -1,4 +1,4 @@
-// sacenv_board_core.h — what the scoreboard kernels (sacenv_episodes.hip) share: the board's
+// sacenv_board_core.h — what the scoreboard kernels (sacenv_board.hip) share: the board's
 // layout and numpy's mean of up to 128 doubles. Plain C++ outside hipcc, so the mean can be
 // compiled for the host and held against numpy there (tests/test_scoreboard_cpu.py).
 #ifndef SACENV_BOARD_CORE_H
@@ -9,6 +9,7 @@
 #include "sacenv_scoreboard.h"
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define SACENV_BOARD_HD __host__ __device__ __forceinline__
 #else
 #define SACENV_BOARD_HD inline

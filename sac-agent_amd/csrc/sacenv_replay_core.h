@@ -10,10 +10,7 @@
 #include <stdint.h>
 
 #include "sacenv.h"
-
-namespace {
-constexpr int kWave = 64;
-}  // namespace
+#include "sacenv_wave_core.h"   // kWave, status()
 
 #include "mt19937.h"
 
@@ -369,11 +366,6 @@ RB make_rb(const SacenvReplayParams& p, void* arena) {
   r.b = static_cast<char*>(arena);
   replay_layout(p, &r.L);
   return r;
-}
-
-int status() {
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? SACENV_OK : (int)err;
 }
 
 }  // namespace

@@ -11,26 +11,24 @@
 //                    record; lane 0 commits the header.
 //   k_select_copy    grid (chunks, P): the workgroups of a member whose source_now is < 0 exit
 //                    at once; the others copy the source's slab over the member's, 16 B per lane
-//                    and access, as k_board_finish (sacenv_episodes.hip) copies a snapshot.
+//                    and access, as k_board_finish (sacenv_board.hip) copies a snapshot.
 // No atomics: the state's and the slabs' bytes are the same from run to run.
 
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
 
 #include "sacenv_board_core.h"
 #include "sacenv_philox.h"
 #include "sacenv_selection.h"
+#include "sacenv_wave_core.h"
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kMaxP = SACENV_SELECT_MAX_MEMBERS;
 constexpr int kCopyThreads = SACENV_SELECT_COPY_THREADS;
-constexpr int kCopyUnroll = SACENV_SELECT_COPY_UNROLL;
 constexpr int kCopyChunks = SACENV_SELECT_COPY_CHUNKS;
 
 static_assert(kMaxP == kWave, "one lane per member");
+static_assert(SACENV_SELECT_COPY_UNROLL == kSlabLoads, "the header's grid rule is slab_copy's");
 static_assert(kMaxP <= SACENV_BOARD_MAX_MEMBERS, "the board holds every member");
 static_assert(sizeof(SacenvSelectMember) == SACENV_SELECT_MEMBER_BYTES, "the member record is 64 B");
 static_assert(SACENV_SELECT_HEADER_BYTES % 16 == 0 && SACENV_SELECT_MEMBER_BYTES % 16 == 0, "16-B records");
@@ -55,20 +53,12 @@ __device__ __forceinline__ SacenvSelectMember* select_member(char* state, const 
   return reinterpret_cast<SacenvSelectMember*>(state + SACENV_SELECT_HEADER_BYTES) + m;
 }
 
-__device__ __forceinline__ void store16(void* p, const uint64_t a, const uint64_t b) {
-  *reinterpret_cast<ulong2*>(p) = ulong2{a, b};
-}
-
 // lane j's value for every lane (j the same in all lanes: two v_readlane, no LDS)
 __device__ __forceinline__ double lane_value(const double x, const int j) {
   const uint64_t b = (uint64_t)__double_as_longlong(x);
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, j);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), j);
   return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-__device__ __forceinline__ uint64_t pack32(const int32_t lo, const int32_t hi) {
-  return (uint64_t)(uint32_t)lo | ((uint64_t)(uint32_t)hi << 32);
 }
 
 __global__ __launch_bounds__(kWave) void k_select_decide(const Decide a) {
@@ -154,19 +144,7 @@ __global__ __launch_bounds__(kCopyThreads) void k_select_copy(const char* __rest
   const int32_t s =
       (reinterpret_cast<const SacenvSelectMember*>(state + SACENV_SELECT_HEADER_BYTES) + m)->source_now;
   if (s < 0 || s >= (int)gridDim.y || s == m) return;   // (a state of garbage moves nothing out of bounds)
-  const float4* __restrict__ src = weights + (int64_t)s * vecs;
-  float4* __restrict__ dst = weights + (int64_t)m * vecs;
-  const int64_t stride = (int64_t)gridDim.x * kCopyThreads;
-  int64_t i = (int64_t)blockIdx.x * kCopyThreads + threadIdx.x;
-  static_assert(kCopyUnroll == 4, "four loads in flight per lane, written out");
-  for (; i + 3 * stride < vecs; i += 4 * stride) {   // (named values: an array of them is put into LDS)
-    const float4 v0 = src[i], v1 = src[i + stride], v2 = src[i + 2 * stride], v3 = src[i + 3 * stride];
-    dst[i] = v0;
-    dst[i + stride] = v1;
-    dst[i + 2 * stride] = v2;
-    dst[i + 3 * stride] = v3;
-  }
-  for (; i < vecs; i += stride) dst[i] = src[i];
+  slab_copy<kCopyThreads>(weights + (int64_t)s * vecs, weights + (int64_t)m * vecs, vecs);
 }
 
 // the empty state: lane m writes member m's record, lane 0 the header too
@@ -196,11 +174,6 @@ int check_select(const SacenvSelect* s) {
   for (int k = 0; k < 4; ++k)
     if (!isfinite(s->lo[k]) || !isfinite(s->hi[k]) || s->lo[k] > s->hi[k]) return SACENV_E_RANGE;
   return SACENV_OK;
-}
-
-int status() {
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? SACENV_OK : (int)err;
 }
 
 }  // namespace
@@ -253,9 +226,7 @@ int sacenv_select_step(const SacenvSelect* s, const void* board, void* state, fl
   const hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_select_decide, dim3(1), dim3(kWave), 0, st, a);
   const int64_t vecs = s->member_floats / 4;
-  const int64_t per = (int64_t)kCopyThreads * kCopyUnroll;
-  int64_t chunks = (vecs + per - 1) / per;
-  chunks = chunks > kCopyChunks ? kCopyChunks : chunks;
+  const int64_t chunks = slab_chunks(vecs, kCopyThreads, kCopyChunks);
   hipLaunchKernelGGL(k_select_copy, dim3((uint32_t)chunks, (uint32_t)s->members), dim3(kCopyThreads), 0, st,
                      static_cast<const char*>(state), reinterpret_cast<float4*>(weights), vecs);
   return status();

@@ -16,15 +16,13 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 BUILD = os.path.join(PKG_ROOT, "build")
 LIB = os.path.join(BUILD, "libsacenv.so")
+# every translation unit of libsacenv.so
 SOURCES = ("sacenv_boat.hip", "sacenv_replay.hip", "sacenv_sac.hip", "sacenv_episodes.hip",
-           "sacenv_sac_pop.hip", "sacenv_replay_pop.hip", "sacenv_noise.hip")
-# SOURCES is the library up to the scoreboard (what a build of the boat workload alone needs);
-# UNITS is every translation unit of libsacenv.so: those and population selection's
-SELECTION_SOURCES = ("sacenv_select.hip",)
-UNITS = SOURCES + SELECTION_SOURCES
+           "sacenv_sac_pop.hip", "sacenv_replay_pop.hip", "sacenv_noise.hip", "sacenv_board.hip",
+           "sacenv_select.hip")
 HEADERS = ("mt19937.h", "sacenv_replay_core.h", "sacenv_sac_core.h", "sacenv_philox.h",
            "sacenv_boat_arena.h", "sacenv_boat_math.h", "sacenv_boat_wind.h", "sacenv_boat_draw.h",
-           "sacenv_toys.h", "sacenv_boat_owner.h", "sacenv_board_core.h")
+           "sacenv_toys.h", "sacenv_boat_owner.h", "sacenv_board_core.h", "sacenv_wave_core.h")
 PUBLIC_HEADERS = ("sacenv.h", "sacenv_episodes.h", "sacenv_population.h", "sacenv_population_replay.h",
                   "sacenv_noise.h", "sacenv_scoreboard.h", "sacenv_selection.h")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
@@ -33,7 +31,7 @@ HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 
 def deps() -> list[tuple[str, str]]:
     """(path relative to the repo root, absolute path) of every input file."""
-    rel = [os.path.join("sac-agent_amd", "csrc", f) for f in UNITS + HEADERS]
+    rel = [os.path.join("sac-agent_amd", "csrc", f) for f in SOURCES + HEADERS]
     rel += [os.path.join("include", h) for h in PUBLIC_HEADERS]
     return [(r, os.path.join(REPO_ROOT, r)) for r in rel]
 

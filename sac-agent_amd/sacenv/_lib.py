@@ -414,6 +414,12 @@ def cuda_device(device, who: str):
     return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
 
 
+def stream_handle(device) -> C.c_void_p:
+    """The ``void* stream`` of an entry point: torch's current stream on ``device``."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def check(rc: int) -> None:
     if rc != 0:
         msg = load().sacenv_error_string(rc).decode()

@@ -62,8 +62,7 @@ class PolicyNoise:
             d.out = t.data_ptr() if size else None
             out.append(t)
             off += size
-        stream_h = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self._normal(P, self._seeds, len(reqs), desc, stream_h))
+        _lib.check(self._normal(P, self._seeds, len(reqs), desc, _lib.stream_handle(self.device)))
         return out
 
     def normal(self, stream: int, call: int, n: int, calls: int = 1) -> torch.Tensor:

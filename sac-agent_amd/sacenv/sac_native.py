@@ -158,7 +158,7 @@ class _SacCore:
         self.noise = None if noise_seeds is None else PolicyNoise(noise_seeds, self.device)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_handle(self.device)
 
     def sync(self) -> None:
         """Refresh the kernels' transposed 256x256 layers after a host write to the weights."""

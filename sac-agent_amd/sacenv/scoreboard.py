@@ -75,11 +75,8 @@ class MemberScoreboard:
         if population is not None:
             self.snapshot = torch.zeros((self.P, member_floats), dtype=torch.float32, device=self.device)
         self._views = {}
-        _lib.check(self._init(C.byref(self.params), self.board.data_ptr(), self._stream()))
+        _lib.check(self._init(C.byref(self.params), self.board.data_ptr(), _lib.stream_handle(self.device)))
         log.watchers.append(self)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def update(self) -> None:
         """Consume the log's new entries; only enqueues work on the current stream (two
@@ -89,11 +86,11 @@ class MemberScoreboard:
         if self.snapshot is not None:
             w, s = self.population.weights.data_ptr(), self.snapshot.data_ptr()
         _lib.check(self._update(C.byref(self.params), self.log.log.data_ptr(), self.board.data_ptr(), w, s,
-                                self._stream()))
+                                _lib.stream_handle(self.device)))
 
     def rewind(self) -> None:
         """The log was emptied (``EpisodeLog.drain`` calls this): start reading at its first entry."""
-        _lib.check(self._rewind(C.byref(self.params), self.board.data_ptr(), self._stream()))
+        _lib.check(self._rewind(C.byref(self.params), self.board.data_ptr(), _lib.stream_handle(self.device)))
 
     # ---- the host's view (each synchronises)
 

@@ -84,11 +84,9 @@ class PopulationSelection:
         need = C.c_int64()
         _lib.check(self._bytes(C.byref(self.params), C.byref(need)))
         self.state = torch.zeros(need.value, dtype=torch.uint8, device=self.device)
-        _lib.check(self._init(C.byref(self.params), population._hp, self.state.data_ptr(), self._stream()))
+        _lib.check(self._init(C.byref(self.params), population._hp, self.state.data_ptr(),
+                              _lib.stream_handle(self.device)))
         self._committed = np.zeros(self.P, np.int64)   # each member's `replaced` at the last commit
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _check_population(self) -> None:
         pop = self.population
@@ -106,7 +104,7 @@ class PopulationSelection:
         until ``commit``."""
         self._check_population()
         _lib.check(self._step(C.byref(self.params), self.board.board.data_ptr(), self.state.data_ptr(),
-                              self.population.weights.data_ptr(), self._stream()))
+                              self.population.weights.data_ptr(), _lib.stream_handle(self.device)))
 
     def commit(self) -> list:
         """Read the state back (the one synchronisation) and give every member replaced since

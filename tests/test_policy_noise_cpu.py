@@ -55,7 +55,9 @@ def test_library_exports_the_noise_entry_point(built_lib):
     assert os.path.join("include", "sacenv_noise.h") in rel
     assert os.path.join("sac-agent_amd", "csrc", "sacenv_noise.hip") in rel
     assert os.path.join("sac-agent_amd", "csrc", "sacenv_philox.h") in rel
-    assert "sacenv_noise.hip" in _build.SOURCES and len(_build.SOURCES) == 7
+    assert "sacenv_noise.hip" in _build.SOURCES and len(set(_build.SOURCES)) == len(_build.SOURCES)
+    # one list: the library's units are the .hip files of csrc/, all of them and no other
+    assert set(_build.SOURCES) == {f for f in os.listdir(_build.CSRC) if f.endswith(".hip")}
     assert "sacenv_philox.h" in _build.HEADERS
     # one copy of the generator: the replay unit and the noise unit include the shared header
     for f in ("sacenv_replay.hip", "sacenv_noise.hip"):

@@ -1,7 +1,8 @@
 """The population scoreboard without a GPU (include/sacenv_scoreboard.h).
 
 * the header's functions are ``_lib.SCOREBOARD_EXPORTS``, beside the 49 of include/sacenv.h and
-  every older optional header; the build lists the new headers and still has seven sources;
+  every older optional header; the build lists the unit and its headers, and the episode log's
+  unit defines none of them;
 * ``SacenvBoard`` and the 128-B member record have the layout of their ctypes and numpy mirrors;
 * the Python restatement (tests/scoreboard_oracle.py) against the literal lines of the
   reference (a list and ``np.mean(history[-L:])``), field by field and bit for bit, and the C++
@@ -63,7 +64,14 @@ def test_header_and_exports(built_lib):
     rel = [r for r, _ in _build.deps()]
     assert os.path.join("include", "sacenv_scoreboard.h") in rel
     assert os.path.join("sac-agent_amd", "csrc", "sacenv_board_core.h") in rel
-    assert len(_build.SOURCES) == 7
+    assert "sacenv_board.hip" in _build.SOURCES
+    assert os.path.join("sac-agent_amd", "csrc", "sacenv_board.hip") in rel
+    text = open(os.path.join(_build.CSRC, "sacenv_board.hip")).read()
+    for inc in ("sacenv_board_core.h", "sacenv_scoreboard.h"):
+        assert f'#include "{inc}"' in text
+    for n in names:                                          # each entry point is defined there, once
+        assert len(re.findall(rf"^int {n}\(", text, re.M)) == 1, n
+    assert "sacenv_board_" not in open(os.path.join(_build.CSRC, "sacenv_episodes.hip")).read()
     import sacenv
     from sacenv.scoreboard import MemberScoreboard
     assert sacenv.MemberScoreboard is MemberScoreboard and "MemberScoreboard" in sacenv.__all__

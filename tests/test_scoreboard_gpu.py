@@ -269,7 +269,10 @@ def _three_calls(P=3, epm=64):
     return out
 
 
-@pytest.mark.parametrize("member_floats", (4, 1028, None))
+# one vector; a workgroup's share and one more; one group of four vectors past the clamp of 64
+# workgroups of 256 lanes with four loads each (the unrolled loop once, then the tail in four
+# lanes); the real slab
+@pytest.mark.parametrize("member_floats", (4, 1028, 4 * (256 * 4 * 64 + 4), None))
 def test_snapshot_copies_the_members_that_saved(gpu, built_lib, member_floats):
     P, L = 3, 50
     mf = _real_member_floats() if member_floats is None else member_floats

@@ -72,12 +72,14 @@ def test_header_and_exports(built_lib):
     rel = [r for r, _ in _build.deps()]
     assert os.path.join("include", "sacenv_selection.h") in rel
     assert os.path.join("sac-agent_amd", "csrc", "sacenv_select.hip") in rel
-    assert "sacenv_select.hip" in _build.UNITS and set(_build.SOURCES) < set(_build.UNITS)
+    assert os.path.join("sac-agent_amd", "csrc", "sacenv_wave_core.h") in rel
+    assert "sacenv_select.hip" in _build.SOURCES
     text = open(os.path.join(_build.CSRC, "sacenv_select.hip")).read()
-    for inc in ("sacenv_board_core.h", "sacenv_philox.h", "sacenv_selection.h"):
+    for inc in ("sacenv_board_core.h", "sacenv_philox.h", "sacenv_selection.h", "sacenv_wave_core.h"):
         assert f'#include "{inc}"' in text
     assert "void philox4x64_10" not in text                  # one copy of the generator
-    assert not re.search(r"atomic\w*\s*\(", text)            # no atomics: the bytes are the same run to run
+    shared = open(os.path.join(_build.CSRC, "sacenv_wave_core.h")).read()    # (the copy's body lives there)
+    assert not re.search(r"atomic\w*\s*\(", text + shared)   # no atomics: the bytes are the same run to run
     import sacenv
     from sacenv.selection import PopulationSelection
     assert sacenv.PopulationSelection is PopulationSelection and "PopulationSelection" in sacenv.__all__
