@@ -14,7 +14,7 @@ as OS processes, three at a time; here they are the members of one ``NativeSACPo
 
     python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
         [--replay population|members] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
-        [--select-every K [--quantile Q] [--min-episodes E] [--select-seed 0]]
+        [--select-every K [--quantile Q] [--min-episodes E] [--select-seed 0]] [--keep-traces DIR]
 
 ``--noise counter`` gives member m the noise seed ``--noise-seed`` + m (``sacenv.PolicyNoise``): the
 act draw and both learn draws of an iteration come from one launch for all members, and member m's
@@ -40,6 +40,12 @@ times 0.8 or 1.2 and clipped to the search ranges. One line is printed per repla
 JSON line gains ``selection`` (per member: rank, times replaced, parent, current values) and
 ``replacements``. The table's drawn values are then the members' LAST ones. Without the flag
 nothing changes.
+
+``--keep-traces DIR`` keeps the episodes the reference would render: a ``BestEpisodes`` holds the
+recent steps of every env on the device and, whenever an episode ends with a score above its
+member's best, keeps its rows (one ``update`` per iteration, two launches). At the end its table is
+printed, each member's best episode goes to DIR/member_<m>/episodes/episode_0_data.csv in the
+reference's format, and the JSON line gains ``traces``. Without the flag nothing changes.
 """
 from __future__ import annotations
 
@@ -81,6 +87,9 @@ def main(argv=None):
                     help="episodes a member finishes after a replacement before it is ranked again "
                          "(default: --lookback)")
     ap.add_argument("--select-seed", type=int, default=0, help="seed of the selection's draws")
+    ap.add_argument("--keep-traces", default=None, metavar="DIR",
+                    help="keep each member's best episode step by step on the device; write them to DIR as the "
+                         "reference's episode CSVs")
     ap.add_argument("--max-episode-steps", type=int, default=500)
     args = ap.parse_args(argv)
     P, N = args.members, args.envs_per_member
@@ -113,6 +122,10 @@ def main(argv=None):
         scores = board if board is not None else MemberScoreboard(log, P, N, lookback=args.lookback)
         selection = PopulationSelection(scores, pop, quantile=args.quantile, min_episodes=args.min_episodes,
                                         seed=args.select_seed)
+    traces = None
+    if args.keep_traces:
+        from sacenv import BestEpisodes
+        traces = BestEpisodes(env, members=P, envs_per_member=N)
     replacements = []
     # terminal as main.py:83-88 stores it: each env's last termination, kept per member
     last_term = [torch.zeros(N, dtype=torch.uint8, device=dev) for _ in range(P)]
@@ -126,6 +139,8 @@ def main(argv=None):
         a = pop.choose_action(obs.view(P, N, -1), eps=eps)
         env.step(a.view(-1))
         log.update()
+        if traces is not None:
+            traces.update(a.view(-1))
         if pooled:  # member m's rows are envs [m N, (m + 1) N): the env's outputs as they lie
             replay.store_env_step(obs, a, env)
         for m in range(0 if pooled else P):
@@ -179,6 +194,16 @@ def main(argv=None):
                   f"{fmt(row['avg_score'])} {row['saves']:>6} {str(row['last_save_step']):>10}")
         kept = board.save_models(args.keep_best)
         print(f"best member {board.best_member()}; snapshots of members {kept} in {args.keep_best}")
+    trace_table = None
+    if traces is not None:
+        trace_table = traces.table()
+        print("best episodes:")
+        print(f"{'member':>6} {'Score':>12} {'env':>8} {'end step':>10} {'length':>7} {'rows':>6} {'replaced':>8}  ending")
+        for row in trace_table:
+            print(f"{row['member']:>6} {fmt(row['score'])} {str(row['env']):>8} {str(row['end_step']):>10} "
+                  f"{row['length']:>7} {row['rows']:>6} {row['replaced']:>8}  {row['term'] or '-'}")
+        written = traces.save_csv(args.keep_traces)
+        print(f"best episodes of members {written} in {args.keep_traces}")
     out = {"pipeline": "population act + VecBoatEnv.step + " + ("population store + population sample" if pooled else
                                                                   "per-member store + per-member sample")
                        + " + population learn", "replay": args.replay, "noise": args.noise,
@@ -189,6 +214,8 @@ def main(argv=None):
         out.update(device_table=device_table, kept=kept, best_member=board.best_member())
     if selection is not None:
         out.update(selection=selection.table(), replacements=replacements)
+    if traces is not None:
+        out.update(traces=trace_table)
     print(json.dumps(out))
     return out
 

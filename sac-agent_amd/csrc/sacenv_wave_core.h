@@ -1,5 +1,6 @@
 // sacenv_wave_core.h — what the episode log (sacenv_episodes.hip), the scoreboard
-// (sacenv_board.hip) and population selection (sacenv_select.hip) share: the wave's width, a
+// (sacenv_board.hip), population selection (sacenv_select.hip) and the episode traces
+// (sacenv_traces.hip) share: the wave's width, a
 // lane's rank in a ballot, the 16-B store, the slab copy with its grid, and the launches'
 // outcome (that one the replay units take too). No kernel and no entry point lives here.
 #pragma once

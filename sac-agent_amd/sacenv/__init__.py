@@ -10,7 +10,7 @@ from .spaces import Box
 
 __all__ = ["BoatConfig", "Box", "VecBoatEnv", "BoatEnv", "ParachuteEnv", "CarEnv", "VecToyEnv",
            "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "PopulationReplay", "PolicyNoise",
-           "MemberScoreboard", "PopulationSelection", "_lib"]
+           "MemberScoreboard", "PopulationSelection", "BestEpisodes", "_lib"]
 
 
 def __getattr__(name):  # lazy: importing torch-dependent classes only when used
@@ -38,4 +38,7 @@ def __getattr__(name):  # lazy: importing torch-dependent classes only when used
     if name == "PopulationSelection":
         from .selection import PopulationSelection
         return PopulationSelection
+    if name == "BestEpisodes":
+        from .traces import BestEpisodes
+        return BestEpisodes
     raise AttributeError(name)

@@ -269,6 +269,38 @@ class SelectMember(C.Structure):
                 ("parent", _i32), ("reserved", _i32), ("hp", _d * 4)]
 
 
+# include/sacenv_traces.h (SACENV_TRACES_VERSION 1): the rows of each member's best episode, kept
+# from the step records; beside the ABI of sacenv.h, bound only where the library has them
+TRACES_VERSION = 1
+TRACES_MAX_MEMBERS = 64
+TRACES_MAX_STEPS = 1 << 20
+TRACE_HEADER_BYTES = 64
+TRACE_ROW_BYTES = 64
+TRACE_STEP_BYTES = 52
+TRACES_EXPORTS = ("sacenv_traces_bytes", "sacenv_traces_init", "sacenv_traces_update")
+
+
+class Traces(C.Structure):
+    """SacenvTraces (sacenv_traces.h)."""
+    _fields_ = [("n_envs", _i32), ("n_pad", _i32), ("members", _i32), ("envs_per_member", _i32),
+                ("env_base", _i32), ("max_steps", _i32), ("call_steps", _i32), ("reserved", _i32),
+                ("step0", _i64)]
+
+
+class TraceSteps(C.Structure):
+    """SacenvTraceSteps: one update call's steps."""
+    _fields_ = [("n_steps", _i32), ("reserved", _i32), ("step", _i64), ("rec_stride", _i64),
+                ("obs_off", _i64), ("reward_off", _i64), ("done_off", _i64), ("term_off", _i64),
+                ("final_stride", _i64)]
+
+
+class TraceHeader(C.Structure):
+    """SacenvTraceHeader: the 64 bytes in front of a member's rows."""
+    _fields_ = [("end_step", _i64), ("score", _d), ("env", _i32), ("length", _i32), ("term", C.c_uint32),
+                ("rows", _i32), ("first_row", _i32), ("reserved0", _i32), ("replaced", _i64),
+                ("reserved", _i64 * 2)]
+
+
 _LIB = None
 
 
@@ -364,6 +396,7 @@ def load(path: str | None = None):
         f = getattr(lib, name)
         f.restype, f.argtypes = res, args
     ES, QP, BP, XP = C.POINTER(EpisodeScan), C.POINTER(SacParams), C.POINTER(Board), C.POINTER(Select)
+    TP_ = C.POINTER(Traces)
     optional = (   # the headers beside sacenv.h: (names, argtypes), absent from a library built before them
         (EPISODE_EXPORTS, ([ES, C.POINTER(_i64)], [ES, _p, _p, _p, _p, _i64, _p])),
         (POPULATION_EXPORTS, (
@@ -377,7 +410,9 @@ def load(path: str | None = None):
             [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])),
         (NOISE_EXPORTS, ([_i32, C.POINTER(C.c_uint64), _i32, C.POINTER(NoiseDraw), _p],)),
         (SCOREBOARD_EXPORTS, ([BP, C.POINTER(_i64)], [BP, _p, _p], [BP, _p, _p, _p, _p, _p], [BP, _p, _p])),
-        (SELECTION_EXPORTS, ([XP, C.POINTER(_i64)], [XP, C.POINTER(SacMember), _p, _p], [XP, _p, _p, _p, _p])))
+        (SELECTION_EXPORTS, ([XP, C.POINTER(_i64)], [XP, C.POINTER(SacMember), _p, _p], [XP, _p, _p, _p, _p])),
+        (TRACES_EXPORTS, ([TP_, C.POINTER(_i64), C.POINTER(_i64)], [TP_, _p, _p, _p, _p, _p, _p],
+                          [TP_, C.POINTER(TraceSteps), _p, _p, _p, _p, _p, _p])))
     for names, argtypes in optional:
         assert len(names) == len(argtypes)
         for name, args in zip(names, argtypes):
