@@ -14,7 +14,8 @@ as OS processes, three at a time; here they are the members of one ``NativeSACPo
 
     python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
         [--replay population|members] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
-        [--select-every K [--quantile Q] [--min-episodes E] [--select-seed 0]] [--keep-traces DIR]
+        [--select-every K [--quantile Q] [--min-episodes E] [--select-seed 0]] [--keep-traces DIR
+        [--render DIR [--render-every K]]]
 
 ``--noise counter`` gives member m the noise seed ``--noise-seed`` + m (``sacenv.PolicyNoise``): the
 act draw and both learn draws of an iteration come from one launch for all members, and member m's
@@ -46,6 +47,12 @@ recent steps of every env on the device and, whenever an episode ends with a sco
 member's best, keeps its rows (one ``update`` per iteration, two launches). At the end its table is
 printed, each member's best episode goes to DIR/member_<m>/episodes/episode_0_data.csv in the
 reference's format, and the JSON line gains ``traces``. Without the flag nothing changes.
+
+``--render DIR [--render-every K]`` (with ``--keep-traces``) draws those episodes as main.py -r does:
+at the end an ``EpisodeFrames`` draws every K-th step of each member's best episode on the device
+-- the track, the path so far, the boat at its heading, the action and rudder strip with a cursor --
+and writes DIR/member_<m>/rendering/episode_0.gif; one line is printed and the JSON line gains
+``frames`` (per member the frame count and the file). Without the flag nothing changes.
 """
 from __future__ import annotations
 
@@ -90,8 +97,14 @@ def main(argv=None):
     ap.add_argument("--keep-traces", default=None, metavar="DIR",
                     help="keep each member's best episode step by step on the device; write them to DIR as the "
                          "reference's episode CSVs")
+    ap.add_argument("--render", default=None, metavar="DIR",
+                    help="draw each member's best episode on the device and write it to DIR as a GIF (needs "
+                         "--keep-traces)")
+    ap.add_argument("--render-every", type=int, default=1, metavar="K", help="draw every K-th step and the last")
     ap.add_argument("--max-episode-steps", type=int, default=500)
     args = ap.parse_args(argv)
+    if args.render and not args.keep_traces:
+        ap.error("--render draws the episodes --keep-traces keeps")
     P, N = args.members, args.envs_per_member
     if N < 64 or N % 64:
         raise SystemExit("--envs-per-member must be a multiple of 64 (the act kernel's row block)")
@@ -204,6 +217,15 @@ def main(argv=None):
                   f"{row['length']:>7} {row['rows']:>6} {row['replaced']:>8}  {row['term'] or '-'}")
         written = traces.save_csv(args.keep_traces)
         print(f"best episodes of members {written} in {args.keep_traces}")
+    frame_table = None
+    if args.render:
+        from sacenv import EpisodeFrames
+        frames = EpisodeFrames(traces, every=args.render_every)
+        drawn = frames.save_gif(args.render)
+        frame_table = [{"member": m, "frames": len(frames.frame_steps(m)),
+                        "file": os.path.join(args.render, f"member_{m}", "rendering", "episode_0.gif")
+                        if m in drawn else None} for m in range(P)]
+        print(f"frames of members {drawn} in {args.render}")
     out = {"pipeline": "population act + VecBoatEnv.step + " + ("population store + population sample" if pooled else
                                                                   "per-member store + per-member sample")
                        + " + population learn", "replay": args.replay, "noise": args.noise,
@@ -216,6 +238,8 @@ def main(argv=None):
         out.update(selection=selection.table(), replacements=replacements)
     if traces is not None:
         out.update(traces=trace_table)
+    if frame_table is not None:
+        out.update(frames=frame_table)
     print(json.dumps(out))
     return out
 

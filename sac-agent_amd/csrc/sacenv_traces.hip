@@ -42,6 +42,7 @@
 
 #include "sacenv_traces.h"
 #include "sacenv_wave_core.h"
+#include "sacenv_traces_frames.h"   // the episode frames' kernels (include/sacenv_frames.h); their entry points are below
 
 namespace {
 
@@ -442,6 +443,24 @@ Tr make_tr(const SacenvTraces* t, void* member_buf, void* store) {
   return a;
 }
 
+// ---- the episode frames (include/sacenv_frames.h; the kernels are in sacenv_traces_frames.h)
+
+inline bool fr_finite(const float v) { return v - v == 0.0f; }
+
+int check_frames(const SacenvFrames* f) {
+  if (f == nullptr) return SACENV_E_NULL;
+  if (f->width < SACENV_FRAMES_MIN_DIM || f->width > SACENV_FRAMES_MAX_DIM || f->width % 4 != 0 ||
+      f->height < SACENV_FRAMES_MIN_DIM || f->height > SACENV_FRAMES_MAX_DIM || f->strip < 2 ||
+      f->height - f->strip < 8 || f->members < 1 || f->members > SACENV_TRACES_MAX_MEMBERS || f->max_steps < 1 ||
+      f->max_steps > SACENV_TRACES_MAX_STEPS || f->rad < 1 || f->rad > SACENV_FRAMES_MAX_RAD || f->boat_len < 1 ||
+      f->boat_len > SACENV_FRAMES_MAX_BOAT || f->boat_half < 1 || f->boat_half > SACENV_FRAMES_MAX_BOAT)
+    return SACENV_E_SIZE;
+  if (!fr_finite(f->x0) || !fr_finite(f->y0) || !fr_finite(f->scale_x) || !fr_finite(f->scale_y) || !(f->scale_x > 0.0f) ||
+      !(f->scale_y > 0.0f) || !fr_finite(f->goal_line) || !fr_finite(f->track_width))
+    return SACENV_E_RANGE;
+  return SACENV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -503,6 +522,62 @@ int sacenv_traces_update(const SacenvTraces* t, const SacenvTraceSteps* s, const
   const hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_tr_walk, dim3((uint32_t)a.n_waves), dim3(kWave), 0, st, a);
   hipLaunchKernelGGL(k_tr_pick, dim3((uint32_t)t->members), dim3(kPickThreads), 0, st, a);
+  return status();
+}
+
+int sacenv_frames_bytes(const SacenvFrames* f, int64_t* scratch_bytes, int64_t* frame_bytes) {
+  const int rc = check_frames(f);
+  if (rc) return rc;
+  if (scratch_bytes == nullptr || frame_bytes == nullptr) return SACENV_E_NULL;
+  *scratch_bytes = fr_map_off(f->max_steps, f->width) + 4 * (int64_t)f->width * (f->height - f->strip);
+  *frame_bytes = (int64_t)f->width * f->height;
+  return SACENV_OK;
+}
+
+int sacenv_frames_render(const SacenvFrames* f, const void* member_buf, int32_t member, int64_t first_frame,
+                         int32_t every, int32_t n_frames, void* out, void* scratch, void* stream) {
+  const int rc = check_frames(f);
+  if (rc) return rc;
+  if (member_buf == nullptr || out == nullptr || scratch == nullptr) return SACENV_E_NULL;
+  if (member < 0 || member >= f->members || every < 1 || n_frames < 1 || n_frames > SACENV_FRAMES_MAX_FRAMES)
+    return SACENV_E_SIZE;
+  if (first_frame < 0 || first_frame > ((int64_t)1 << 62) || (uintptr_t)member_buf % 16 != 0 ||
+      (uintptr_t)scratch % 16 != 0 || (uintptr_t)out % 4 != 0)
+    return SACENV_E_RANGE;
+  Fr a = {};
+  a.member = static_cast<const char*>(member_buf) + member_stride(f->max_steps) * member;
+  a.scratch = static_cast<char*>(scratch);
+  a.out = static_cast<uint8_t*>(out);
+  a.first_frame = first_frame;
+  a.W = f->width;
+  a.H = f->height;
+  a.S = f->strip;
+  a.HP = f->height - f->strip;
+  a.R = f->max_steps;
+  a.rad = f->rad;
+  a.rad2 = f->rad * f->rad;
+  a.boat_len = f->boat_len;
+  a.boat_half = f->boat_half;
+  a.every = every;
+  a.n_frames = n_frames;
+  a.blocks_per_frame = (a.H * (a.W / 4) + 255) / 256;   // <= 1024, times n_frames <= 2^20: a grid.x below 2^31
+  a.inv_wq = fr_inverse((uint32_t)(a.W / 4));
+  a.inv_hp = fr_inverse((uint32_t)a.HP);
+  a.x0 = f->x0;
+  a.y0 = f->y0;
+  a.sx = f->scale_x;
+  a.sy = f->scale_y;
+  a.goal_line = f->goal_line;
+  a.track_width = f->track_width;
+  FrDir dir;
+  static_assert(sizeof(dir.v) == sizeof(f->dir), "the direction table goes to the points launch by value");
+  memcpy(dir.v, f->dir, sizeof(dir.v));
+  const hipStream_t st = (hipStream_t)stream;
+  const int32_t items = a.R + 1 > a.W ? a.R + 1 : a.W;   // a thread per row and per strip column
+  hipLaunchKernelGGL(k_fr_points, dim3((uint32_t)((items + 255) / 256)), dim3(256), 0, st, a, dir);
+  hipLaunchKernelGGL(k_fr_cover, dim3((uint32_t)((a.W + kFrTile - 1) / kFrTile), (uint32_t)((a.HP + kFrTile - 1) / kFrTile)),
+                     dim3(kFrThreads), 0, st, a);
+  hipLaunchKernelGGL(k_fr_compose, dim3((uint32_t)a.blocks_per_frame * (uint32_t)n_frames), dim3(256), 0, st, a);
   return status();
 }
 

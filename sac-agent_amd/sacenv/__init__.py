@@ -10,7 +10,7 @@ from .spaces import Box
 
 __all__ = ["BoatConfig", "Box", "VecBoatEnv", "BoatEnv", "ParachuteEnv", "CarEnv", "VecToyEnv",
            "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "PopulationReplay", "PolicyNoise",
-           "MemberScoreboard", "PopulationSelection", "BestEpisodes", "_lib"]
+           "MemberScoreboard", "PopulationSelection", "BestEpisodes", "EpisodeFrames", "_lib"]
 
 
 def __getattr__(name):  # lazy: importing torch-dependent classes only when used
@@ -41,4 +41,7 @@ def __getattr__(name):  # lazy: importing torch-dependent classes only when used
     if name == "BestEpisodes":
         from .traces import BestEpisodes
         return BestEpisodes
+    if name == "EpisodeFrames":
+        from .frames import EpisodeFrames
+        return EpisodeFrames
     raise AttributeError(name)

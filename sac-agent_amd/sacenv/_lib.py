@@ -301,6 +301,28 @@ class TraceHeader(C.Structure):
                 ("reserved", _i64 * 2)]
 
 
+# include/sacenv_frames.h (SACENV_FRAMES_VERSION 1): the frames of a member's kept episode, drawn
+# from the member buffer of the traces; beside the ABI of sacenv.h, bound only where the library
+# has them
+FRAMES_VERSION = 1
+FRAMES_MIN_DIM, FRAMES_MAX_DIM = 16, 1024
+FRAMES_MAX_FRAMES = 1 << 20
+FRAMES_MAX_RAD, FRAMES_MAX_BOAT = 256, 1024
+FRAMES_CHUNK = 128
+FRAMES_WATER = 32
+(FRAMES_OUTSIDE, FRAMES_BOUNDARY, FRAMES_GOAL, FRAMES_PATH, FRAMES_BOAT, FRAMES_STRIP, FRAMES_ZERO,
+ FRAMES_RUDDER, FRAMES_ACTION, FRAMES_CURSOR, FRAMES_COLOURS) = range(32, 43)
+FRAMES_EXPORTS = ("sacenv_frames_bytes", "sacenv_frames_render")
+
+
+class Frames(C.Structure):
+    """SacenvFrames (sacenv_frames.h)."""
+    _fields_ = [("width", _i32), ("height", _i32), ("strip", _i32), ("members", _i32), ("max_steps", _i32),
+                ("rad", _i32), ("boat_len", _i32), ("boat_half", _i32), ("x0", C.c_float), ("y0", C.c_float),
+                ("scale_x", C.c_float), ("scale_y", C.c_float), ("goal_line", C.c_float),
+                ("track_width", C.c_float), ("dir", (C.c_int16 * 2) * 256)]
+
+
 _LIB = None
 
 
@@ -412,7 +434,9 @@ def load(path: str | None = None):
         (SCOREBOARD_EXPORTS, ([BP, C.POINTER(_i64)], [BP, _p, _p], [BP, _p, _p, _p, _p, _p], [BP, _p, _p])),
         (SELECTION_EXPORTS, ([XP, C.POINTER(_i64)], [XP, C.POINTER(SacMember), _p, _p], [XP, _p, _p, _p, _p])),
         (TRACES_EXPORTS, ([TP_, C.POINTER(_i64), C.POINTER(_i64)], [TP_, _p, _p, _p, _p, _p, _p],
-                          [TP_, C.POINTER(TraceSteps), _p, _p, _p, _p, _p, _p])))
+                          [TP_, C.POINTER(TraceSteps), _p, _p, _p, _p, _p, _p])),
+        (FRAMES_EXPORTS, ([C.POINTER(Frames), C.POINTER(_i64), C.POINTER(_i64)],
+                          [C.POINTER(Frames), _p, _i32, _i64, _i32, _i32, _p, _p, _p])))
     for names, argtypes in optional:
         assert len(names) == len(argtypes)
         for name, args in zip(names, argtypes):
