@@ -13,9 +13,18 @@ as OS processes, three at a time; here they are the members of one ``NativeSACPo
 * an ``EpisodeLog`` on the env; an episode of env e belongs to member e // N.
 
     python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
-        [--replay population|members] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
+        [--replay population|members] [--share-replay K] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
         [--select-every K [--quantile Q] [--min-episodes E] [--select-seed 0]] [--keep-traces DIR
         [--render DIR [--render-every K]]]
+
+``--share-replay K`` (with ``--replay population``) pools the members' experience: K of the
+``--batch`` rows every member learns from are drawn from all members' buffers, the other rows from
+its own (``PopulationReplay.sample(pool_rows=K)``, include/sacenv_population_share.h: still two
+launches per sample). A stored row is the env's own (obs, action, reward, obs', terminal), so it is
+valid data for every member; a member starts to learn once its own buffer holds a batch, as
+before. With K > 0 a member's run depends on the other members' rows, so it is no longer the run
+that member makes alone. The JSON line gains ``pool_rows``; with 0 the run is the one without the
+flag, and without the flag nothing changes.
 
 ``--noise counter`` gives member m the noise seed ``--noise-seed`` + m (``sacenv.PolicyNoise``): the
 act draw and both learn draws of an iteration come from one launch for all members, and member m's
@@ -80,6 +89,9 @@ def main(argv=None):
     ap.add_argument("--save", default=None, help="directory for the members' checkpoints")
     ap.add_argument("--replay", choices=("population", "members"), default="population",
                     help="one PopulationReplay for all members, or one DeviceReplayBuffer per member")
+    ap.add_argument("--share-replay", type=int, default=None, metavar="K",
+                    help="K of every member's batch rows are drawn from all members' buffers (0: its own only; "
+                         "needs --replay population)")
     ap.add_argument("--noise", choices=("torch", "counter"), default="torch",
                     help="policy noise from torch's stream, or counter-based with one seed per member")
     ap.add_argument("--noise-seed", type=int, default=0, help="member m's noise seed is this + m")
@@ -105,6 +117,11 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.render and not args.keep_traces:
         ap.error("--render draws the episodes --keep-traces keeps")
+    share = args.share_replay or 0
+    if not 0 <= share <= args.batch:
+        ap.error("--share-replay takes 0 to --batch rows")
+    if share and args.replay != "population":
+        ap.error("--share-replay draws from the one arena of --replay population")
     P, N = args.members, args.envs_per_member
     if N < 64 or N % 64:
         raise SystemExit("--envs-per-member must be a multiple of 64 (the act kernel's row block)")
@@ -118,6 +135,7 @@ def main(argv=None):
     if pooled:  # the members' buffers in one arena, with the seeds the per-member buffers get
         replay = PopulationReplay(P, configs[0].max_size, (11,), 1, device=dev, seeds=list(range(P)))
     pop = NativeSACPopulation(dev, configs, init_seeds=list(range(P)), buffer_seeds=list(range(P)), replay=replay,
+                              pool_rows=share,
                               noise_seeds=[args.noise_seed + m for m in range(P)] if args.noise == "counter" else None)
     for m, mem in enumerate(pop.members):
         print(f"member {m}: " + json.dumps(mem.hpset()))
@@ -232,6 +250,8 @@ def main(argv=None):
            "members": P, "envs_per_member": N, "iters": args.iters, "batch": args.batch,
            "env_steps_per_s": P * N * args.iters / el, "ms_per_iter": el / args.iters * 1e3,
            "losses": None if losses is None else losses.tolist(), "table": table}
+    if args.share_replay is not None:
+        out.update(pool_rows=share)
     if board is not None:
         out.update(device_table=device_table, kept=kept, best_member=board.best_member())
     if selection is not None:

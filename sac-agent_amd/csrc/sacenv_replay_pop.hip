@@ -17,9 +17,13 @@
 // above all the staged, side and stand-in kernels of the timed replay path, are compiled
 // where they were, alone (tools/kernel_diff.py; DESIGN.md §4.6.1 has the result and the
 // resource table).
+//
+// The pooled sample (include/sacenv_population_share.h) lives here too: two
+// kernels of their own, k_rb_draw_pool and k_rb_gather_pool, after the five above.
 #include "sacenv_replay_core.h"
 
 #include "sacenv_population_replay.h"
+#include "sacenv_population_share.h"
 
 namespace {
 
@@ -78,6 +82,168 @@ __global__ void __launch_bounds__(256) k_rb_gather_pop(SacenvReplayParams p, RB 
   gather_body(p, member_rb(r, member_bytes, m), batch, idx + rows, st != nullptr ? st + rows * D : nullptr,
               ac != nullptr ? ac + rows * A : nullptr, rw != nullptr ? rw + rows : nullptr,
               ns != nullptr ? ns + rows * D : nullptr, tm != nullptr ? tm + rows : nullptr, Shard{0, 0, 0});
+}
+
+// ---------------------------------------------------------------------------
+// The pooled sample (include/sacenv_population_share.h): member m draws B - K rows of its own
+// ring and K rows of the whole arena from its own stream, and the gather reads each row from
+// its owner's slab. Both kernels are new bodies: draw_many_body and gather_body, and every
+// kernel above, are as they were.
+
+// One masked-rejection fill on the workgroup's key block: `count` accepted words (w & mask <=
+// rng, rng >= 1) from position `pos` on, in order, to out[0, count) through `put`; the stream
+// stops after the last accepted word. The round of draw_many_body -- a whole 624-word block
+// tempered and tested at once, thread i word i, accepted words ranked by a ballot per wave and
+// a prefix over the waves -- as a loop of its own, so that two fills with different ranges and
+// counts run back to back on one block pair. Every thread of the workgroup calls it with the
+// same arguments.
+struct DrawBlock {
+  uint32_t (*blk)[kMtN];  // LDS [2][kMtN]
+  int* wcnt;              // LDS [kDrawThreads / kWave]
+  int* s_end;             // LDS
+  int cur, pos;
+  bool advanced;
+};
+
+template <class Put>
+__device__ __forceinline__ void fill_masked(DrawBlock& d, uint32_t rng, int count, const Put& put) {
+  constexpr int kWaves = kDrawThreads / kWave;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  uint32_t mask = rng;
+  mask |= mask >> 1;
+  mask |= mask >> 2;
+  mask |= mask >> 4;
+  mask |= mask >> 8;
+  mask |= mask >> 16;
+  int filled = 0;
+  for (;;) {
+    if (d.pos >= kMtN) {
+      mt_twist_block(d.blk[d.cur], d.blk[d.cur ^ 1], tid);
+      d.cur ^= 1;
+      d.pos = 0;
+      d.advanced = true;
+    }
+    const bool valid = tid >= d.pos && tid < kMtN;
+    const uint32_t w = valid ? (mt_temper(d.blk[d.cur][tid]) & mask) : 0u;
+    const bool acc = valid && w <= rng;
+    const unsigned long long bal = __ballot(acc);
+    if (lane == 0) d.wcnt[wv] = __popcll(bal);
+    __syncthreads();
+    int excl = 0, total = 0;
+#pragma unroll
+    for (int q = 0; q < kWaves; ++q) {
+      const int v = d.wcnt[q];
+      excl += q < wv ? v : 0;
+      total += v;
+    }
+    const int rank = excl + __popcll(bal & ((1ull << lane) - 1ull));
+    const int take = count - filled;
+    if (acc && rank < take) put(filled + rank, w);
+    const bool done = total >= take;  // the take-th accepted word ends the fill
+    if (done && acc && rank == take - 1) *d.s_end = tid;
+    __syncthreads();  // s_end is written; wcnt is rewritten by the next round
+    if (done) {
+      d.pos = *d.s_end + 1;
+      __syncthreads();  // (s_end is rewritten by the next fill)
+      return;
+    }
+    filled += total;
+    d.pos = kMtN;
+  }
+}
+
+// RandomState_m.choice(s, batch - pool) then RandomState_m.choice(P * s, pool) on member m's
+// stream at its own count, as global rows owner * M + row into idx[0, batch). One workgroup.
+__device__ __forceinline__ void draw_pool_body(const SacenvReplayParams& p, const RB& r, uint32_t m, uint32_t P,
+                                               int batch, int pool, int64_t* __restrict__ idx) {
+  __shared__ uint32_t blk[2][kMtN];
+  __shared__ int wcnt[kDrawThreads / kWave];
+  __shared__ int s_end;
+  const int tid = threadIdx.x;
+  DrawBlock d{blk, wcnt, &s_end, 0, *r.pos(), false};
+  if (d.pos < 0) {  // a poisoned stream: draw nothing, keep the poison
+    for (int i = tid; i < batch; i += kDrawThreads) idx[i] = -1;
+    return;
+  }
+  for (int i = tid; i < kMtN; i += kDrawThreads) blk[0][i] = r.key()[i];
+  __syncthreads();
+  const int64_t M = p.mem_size, c = *r.cntr();
+  const uint32_t s = (uint32_t)(c < M ? c : M);  // 1 <= s < 2^31 (the host refuses an empty ring)
+  const int own = batch - pool;
+  const int64_t base = (int64_t)m * M;
+  if (own > 0) {
+    if (s <= 1u) {  // numpy's off + 0: no words
+      for (int i = tid; i < own; i += kDrawThreads) idx[i] = base;
+    } else {
+      fill_masked(d, s - 1u, own, [&](int i, uint32_t w) { idx[i] = base + (int64_t)w; });
+    }
+  }
+  if (pool > 0) {
+    const uint64_t range = (uint64_t)P * s;  // <= 2^32 (the host's rule), so rng fits 32 bits
+    int64_t* __restrict__ out = idx + own;
+    if (range <= 1u) {
+      for (int i = tid; i < pool; i += kDrawThreads) out[i] = 0;
+    } else {
+      fill_masked(d, (uint32_t)(range - 1u), pool, [&](int i, uint32_t g) {
+        const uint32_t owner = g / s;  // g < P * s: owner < P, row < s <= M
+        out[i] = (int64_t)owner * M + (int64_t)(g - owner * s);
+      });
+    }
+  }
+  if (d.advanced)
+    for (int i = tid; i < kMtN; i += kDrawThreads) r.key()[i] = blk[d.cur][i];
+  if (tid == 0) *r.pos() = d.pos;
+}
+
+// grid (1, P) x 1 024 threads: one workgroup per member, each on its own key, position and count
+__global__ void __launch_bounds__(kDrawThreads) k_rb_draw_pool(SacenvReplayParams p, RB r, int64_t member_bytes,
+                                                               int batch, int pool, int64_t* __restrict__ idx) {
+  const int64_t m = blockIdx.y;
+  draw_pool_body(p, member_rb(r, member_bytes, m), (uint32_t)m, gridDim.y, batch, pool, idx + m * batch);
+}
+
+// grid (ceil(batch x (D + A + 1) / 256), P): one thread per output element of member m's
+// [batch][..] outputs, in gather_body's column split (state / new_state, action, reward +
+// terminal); the row is row g % M of slab g / M, g the global index; g outside [0, P x M)
+// gives zero bits. P x M <= 2^32 and M < 2^31: 32-bit division.
+__global__ void __launch_bounds__(256) k_rb_gather_pool(SacenvReplayParams p, RB r, int64_t member_bytes, int batch,
+                                                        const int64_t* __restrict__ idx, float* __restrict__ st,
+                                                        float* __restrict__ ac, double* __restrict__ rw,
+                                                        float* __restrict__ ns, uint8_t* __restrict__ tm) {
+  const int64_t m = blockIdx.y, rows = m * batch;
+  const int D = p.obs_dim, A = p.act_dim;
+  const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t nd = (int64_t)batch * D, na = (int64_t)batch * A;
+  const uint32_t M = (uint32_t)p.mem_size;
+  const int64_t top = (int64_t)gridDim.y * p.mem_size;
+  idx += rows;
+  int64_t i, k;
+  int part;
+  if (q < nd) {
+    i = q / D, k = q - i * D, part = 0;
+  } else if (q < nd + na) {
+    const int64_t qq = q - nd;
+    i = qq / A, k = qq - i * A, part = 1;
+  } else if (q < nd + na + batch) {
+    i = q - nd - na, k = 0, part = 2;
+  } else {
+    return;
+  }
+  const int64_t g = idx[i];
+  const bool in = g >= 0 && g < top;
+  const uint32_t gu = in ? (uint32_t)g : 0u, owner = gu / M;
+  const int64_t row = gu - owner * M;
+  const RB ro = member_rb(r, member_bytes, owner);
+  if (part == 0) {
+    const int64_t o = (rows + i) * D + k;
+    if (st) st[o] = in ? ro.state()[row * D + k] : 0.f;
+    if (ns) ns[o] = in ? ro.new_state()[row * D + k] : 0.f;
+  } else if (part == 1) {
+    if (ac) ac[(rows + i) * A + k] = in ? ro.action()[row * A + k] : 0.f;
+  } else {
+    if (rw) rw[rows + i] = in ? ro.reward()[row] : 0.0;
+    if (tm) tm[rows + i] = in ? ro.terminal()[row] : (uint8_t)0;
+  }
 }
 
 int rb_pop_check(const SacenvReplayParams* p, int32_t members) {
@@ -190,4 +356,52 @@ extern "C" int sacenv_replay_pop_gather(const SacenvReplayParams* p, int32_t mem
   if (members == 1)
     return sacenv_replay_gather(p, arena, batch, idx, state, action, reward, new_state, terminal, stream);
   return gather_pop(p, members, make_rb(*p, arena), batch, idx, state, action, reward, new_state, terminal, stream);
+}
+
+// ---- include/sacenv_population_share.h
+
+namespace {
+
+// the family's rules (check_pop_batch_call), then the pool's own: the pool rows, and a pool of
+// at most 2^32 rows (numpy's 32-bit word path; a global row as a 32-bit number in the gather)
+int check_pool_call(const SacenvReplayParams* p, int32_t members, const void* arena, const int64_t* idx,
+                    int32_t batch, int32_t pool_rows, int64_t stored = 1) {
+  const int rc = check_pop_batch_call(p, members, arena, idx, batch, stored);
+  if (rc) return rc;
+  if (pool_rows < 0 || pool_rows > batch) return SACENV_E_SIZE;
+  if ((int64_t)members * p->mem_size > (1LL << 32)) return SACENV_E_SIZE;
+  return SACENV_OK;
+}
+
+int gather_pool(const SacenvReplayParams* p, int32_t members, const RB& r, int32_t batch, const int64_t* idx,
+                float* state, float* action, double* reward, float* new_state, uint8_t* terminal, void* stream) {
+  hipLaunchKernelGGL(k_rb_gather_pool, dim3(gather_blocks(p, batch), members), dim3(256), 0, (hipStream_t)stream,
+                     *p, r, r.L.total_bytes, batch, idx, state, action, reward, new_state, terminal);
+  return status();
+}
+
+}  // namespace
+
+extern "C" int sacenv_replay_pop_sample_pool(const SacenvReplayParams* p, int32_t members, void* arena,
+                                             int32_t batch, int32_t pool_rows, int64_t stored, int64_t* idx,
+                                             float* state, float* action, double* reward, float* new_state,
+                                             uint8_t* terminal, void* stream) {
+  int rc = check_pool_call(p, members, arena, idx, batch, pool_rows, stored);
+  if (rc) return rc;
+  if (batch == 0) return SACENV_OK;
+  const RB r = make_rb(*p, arena);
+  hipLaunchKernelGGL(k_rb_draw_pool, dim3(1, members), dim3(kDrawThreads), 0, (hipStream_t)stream, *p, r,
+                     r.L.total_bytes, batch, pool_rows, idx);
+  if ((rc = status())) return rc;
+  return gather_pool(p, members, r, batch, idx, state, action, reward, new_state, terminal, stream);
+}
+
+extern "C" int sacenv_replay_pop_gather_pool(const SacenvReplayParams* p, int32_t members, void* arena,
+                                             int32_t batch, const int64_t* idx, float* state, float* action,
+                                             double* reward, float* new_state, uint8_t* terminal, void* stream) {
+  const int rc = check_pool_call(p, members, arena, idx, batch, 0);
+  if (rc) return rc;
+  if (batch == 0) return SACENV_OK;
+  return gather_pool(p, members, make_rb(*p, arena), batch, idx, state, action, reward, new_state, terminal,
+                     stream);
 }

@@ -315,6 +315,12 @@ FRAMES_WATER = 32
 FRAMES_EXPORTS = ("sacenv_frames_bytes", "sacenv_frames_render")
 
 
+# include/sacenv_population_share.h (SACENV_REPLAY_SHARE_VERSION 1): part of each member's batch
+# drawn from all members' rings; beside the ABI of sacenv.h, bound only where the library has them
+REPLAY_SHARE_VERSION = 1
+REPLAY_SHARE_EXPORTS = ("sacenv_replay_pop_sample_pool", "sacenv_replay_pop_gather_pool")
+
+
 class Frames(C.Structure):
     """SacenvFrames (sacenv_frames.h)."""
     _fields_ = [("width", _i32), ("height", _i32), ("strip", _i32), ("members", _i32), ("max_steps", _i32),
@@ -436,7 +442,9 @@ def load(path: str | None = None):
         (TRACES_EXPORTS, ([TP_, C.POINTER(_i64), C.POINTER(_i64)], [TP_, _p, _p, _p, _p, _p, _p],
                           [TP_, C.POINTER(TraceSteps), _p, _p, _p, _p, _p, _p])),
         (FRAMES_EXPORTS, ([C.POINTER(Frames), C.POINTER(_i64), C.POINTER(_i64)],
-                          [C.POINTER(Frames), _p, _i32, _i64, _i32, _i32, _p, _p, _p])))
+                          [C.POINTER(Frames), _p, _i32, _i64, _i32, _i32, _p, _p, _p])),
+        (REPLAY_SHARE_EXPORTS, ([RP, _i32, _p, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p],
+                                [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])))
     for names, argtypes in optional:
         assert len(names) == len(argtypes)
         for name, args in zip(names, argtypes):

@@ -106,14 +106,23 @@ class NativeSACPopulation(_SacCore):
     ``lead = (P,)``. ``choose_action``: [P, n, obs_dim] -> [P, n, 1]; ``learn`` takes stacked
     batches (state [P, B, D], ...) or samples each member's own buffer -- P ``DeviceReplayBuffer``s,
     or a ``PopulationReplay`` given as ``replay=`` (two launches, no stacking) -- and returns
-    [P, 4] losses."""
+    [P, 4] losses. ``pool_rows=K`` (with ``replay=``): K of every member's B rows come from all
+    members' rings (include/sacenv_population_share.h); a member still learns once its own ring
+    holds B rows, and with K > 0 its weights depend on the other members' rows."""
 
     def __init__(self, device, configs, *, obs_dim: int = 11, max_action: float = 1.0, init_seeds=None,
                  buffer_seeds=None, with_memory: bool = True, adam_eps: float = 1e-8, replay=None,
-                 noise_seeds=None, _build: bool = True):
+                 noise_seeds=None, pool_rows: int = 0, _build: bool = True):
         cfgs = self.configs = _common_configs(configs)
         P = self.P = len(cfgs)
         cfg = cfgs[0]
+        # rows of every member's batch that learn() draws from all members' rings
+        # (PopulationReplay.sample(pool_rows=)): checked before anything is built or launched
+        self.pool_rows = int(pool_rows)
+        if not 0 <= self.pool_rows <= cfg.batch_size:
+            raise ValueError(f"pool_rows must lie in [0, batch_size = {cfg.batch_size}], got {pool_rows}")
+        if self.pool_rows and replay is None:
+            raise ValueError("pool_rows needs the members' buffers in one arena: give replay=PopulationReplay(...)")
         if P > _lib.POPULATION_MAX_MEMBERS:
             raise ValueError(f"a population holds at most {_lib.POPULATION_MAX_MEMBERS} members, got {P}")
         for name, seeds in (("init_seeds", init_seeds), ("buffer_seeds", buffer_seeds),
@@ -175,7 +184,7 @@ class NativeSACPopulation(_SacCore):
         """One batch per member from its own buffer, as ``learn`` takes them: stacked, or with a
         ``PopulationReplay`` as its two launches write them."""
         if self._pop_replay:
-            return self.memory.sample(self._B, as_bool=False)[:5]
+            return self.memory.sample(self._B, as_bool=False, pool_rows=self.pool_rows)[:5]
         rows = [mem.sample(self._B, as_bool=False)[:5] for mem in self.memory]
         return tuple(torch.stack([r[k] for r in rows]) for k in range(5))
 

@@ -11,6 +11,11 @@ bytes and batches are those of a ``DeviceReplayBuffer`` with member m's seed giv
 rows, bit for bit (tests/test_population_replay_gpu.py); ``export_member`` copies one out.
 
 The members store in lockstep: n rows each per call, one count for all. There is no CPU path.
+
+``sample(B, pool_rows=K)`` draws K of every member's B rows from all members' rings
+(include/sacenv_population_share.h): the rings lie side by side in the arena, so the pooled draw
+is an index computation and a gather across slabs, still two launches. With K > 0 a member's
+batches depend on the other members' rows; with K = 0 nothing changes.
 """
 from __future__ import annotations
 
@@ -73,10 +78,18 @@ class PopulationReplay(_ReplayArena):
                          final_state=env.final_obs.view(P, n, *self.input_shape),
                          last_term=self._env_last_term(env) if reference_terminal else None)
 
-    def sample(self, batch_size: int, as_bool: bool = True):
+    def sample(self, batch_size: int, as_bool: bool = True, pool_rows: int = 0):
         """``DeviceReplayBuffer.sample`` for every member in two launches: (states [P, B, D],
         actions [P, B, A], rewards f64 [P, B], states_, dones [P, B], idx [P, B]), member m's
-        from its own stream. ``as_bool=False``: dones as the kernel writes them (u8 0/1)."""
+        from its own stream. ``as_bool=False``: dones as the kernel writes them (u8 0/1).
+
+        ``pool_rows=K`` > 0 (include/sacenv_population_share.h): the last K rows of every
+        member's batch come from the whole arena -- member m draws ``choice(s, B - K)`` from its
+        own ring, then ``choice(P s, K)`` over all members' rows, on its own stream -- and
+        ``idx`` holds GLOBAL rows, owner x mem_size + row (what ``gather_pool`` takes). With 0
+        the call is what it was: the members' ring rows, through the same entry point."""
+        if pool_rows:
+            return self.sample_pool(batch_size, pool_rows, as_bool)
         B = int(batch_size)
         if self.mem_cntr == 0 and B > 0:
             raise ValueError("a must be greater than 0 unless no samples are taken")
@@ -85,6 +98,36 @@ class PopulationReplay(_ReplayArena):
             self._pp, self.P, self.arena.data_ptr(), B, self.mem_cntr, idx.data_ptr(), st.data_ptr(), ac.data_ptr(),
             rw.data_ptr(), ns.data_ptr(), tm.data_ptr(), self.stream))
         return st, ac, rw, ns, (tm.bool() if as_bool else tm), idx
+
+    def sample_pool(self, batch_size: int, pool_rows: int, as_bool: bool = True):
+        """``sample`` through ``sacenv_replay_pop_sample_pool`` whatever ``pool_rows`` is (0 to
+        ``batch_size``): ``idx`` holds global rows, owner x mem_size + row. With ``pool_rows=0``
+        the batches, and the arena's bytes afterwards, are ``sample``'s, and ``idx`` is
+        ``sample``'s plus m x mem_size."""
+        B, K = int(batch_size), int(pool_rows)
+        if not 0 <= K <= max(B, 0):
+            raise ValueError(f"pool_rows must lie in [0, batch_size = {B}], got {K}")
+        if self.mem_cntr == 0 and B > 0:
+            raise ValueError("a must be greater than 0 unless no samples are taken")
+        fn, = _lib.require(_lib.REPLAY_SHARE_EXPORTS[:1], "sacenv_population_share.h", self.lib)
+        st, ac, rw, ns, tm, idx = self._outputs(B, idx=True)
+        _lib.check(fn(self._pp, self.P, self.arena.data_ptr(), B, K, self.mem_cntr, idx.data_ptr(), st.data_ptr(),
+                      ac.data_ptr(), rw.data_ptr(), ns.data_ptr(), tm.data_ptr(), self.stream))
+        return st, ac, rw, ns, (tm.bool() if as_bool else tm), idx
+
+    def gather_pool(self, idx: torch.Tensor, as_bool: bool = True):
+        """The rows at the given global indices ``[P, B]`` (owner x mem_size + row, as a pooled
+        ``sample`` returns them), for every member, each from its owner's slab (one launch); an
+        index outside ``[0, P x mem_size)`` gives zeros."""
+        fn, = _lib.require(_lib.REPLAY_SHARE_EXPORTS[1:], "sacenv_population_share.h", self.lib)
+        idx = torch.as_tensor(idx).to(device=self.device, dtype=torch.int64).contiguous()
+        if idx.dim() != 2 or idx.shape[0] != self.P:
+            raise ValueError(f"idx must be [{self.P}, B], got {list(idx.shape)}")
+        B = idx.shape[1]
+        st, ac, rw, ns, tm, _ = self._outputs(B)
+        _lib.check(fn(self._pp, self.P, self.arena.data_ptr(), B, idx.data_ptr(), st.data_ptr(), ac.data_ptr(),
+                      rw.data_ptr(), ns.data_ptr(), tm.data_ptr(), self.stream))
+        return st, ac, rw, ns, (tm.bool() if as_bool else tm)
 
     def gather(self, idx: torch.Tensor, as_bool: bool = True):
         """The rows at the given ring indices ``[P, B]``, for every member (one launch); an
