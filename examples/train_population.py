@@ -13,7 +13,7 @@ as OS processes, three at a time; here they are the members of one ``NativeSACPo
 * an ``EpisodeLog`` on the env; an episode of env e belongs to member e // N.
 
     python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
-        [--replay population|members] [--share-replay K] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
+        [--replay population|members] [--share-replay K] [--prioritized [ALPHA]] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
         [--select-every K [--quantile Q] [--min-episodes E] [--select-seed 0]] [--keep-traces DIR
         [--render DIR [--render-every K]]]
 
@@ -25,6 +25,15 @@ valid data for every member; a member starts to learn once its own buffer holds 
 before. With K > 0 a member's run depends on the other members' rows, so it is no longer the run
 that member makes alone. The JSON line gains ``pool_rows``; with 0 the run is the one without the
 flag, and without the flag nothing changes.
+
+``--prioritized [ALPHA]`` (with ``--replay population``, without ``--share-replay``) replays the
+surprising transitions more often: the replay is a ``PrioritizedPopulationReplay``
+(include/sacenv_prioritized_replay.h), every member samples its own rows in proportion to (|TD error|
++ eps)^ALPHA (default 0.6) from a sum tree on the device, new rows enter at the largest priority so
+far, and after each learn the batch's rows take the priorities of the TD errors the learn kernels
+left behind. The importance weights are computed (``replay.last_weights``) but NOT applied in the
+learn; whether prioritizing speeds learning up has not been measured. The JSON line gains
+``prioritized`` (alpha, beta, eps and each member's priority total). Without the flag nothing changes.
 
 ``--noise counter`` gives member m the noise seed ``--noise-seed`` + m (``sacenv.PolicyNoise``): the
 act draw and both learn draws of an iteration come from one launch for all members, and member m's
@@ -92,6 +101,9 @@ def main(argv=None):
     ap.add_argument("--share-replay", type=int, default=None, metavar="K",
                     help="K of every member's batch rows are drawn from all members' buffers (0: its own only; "
                          "needs --replay population)")
+    ap.add_argument("--prioritized", type=float, nargs="?", const=0.6, default=None, metavar="ALPHA",
+                    help="sample every member's rows in proportion to (|TD error| + eps)^ALPHA (needs --replay "
+                         "population; excludes --share-replay)")
     ap.add_argument("--noise", choices=("torch", "counter"), default="torch",
                     help="policy noise from torch's stream, or counter-based with one seed per member")
     ap.add_argument("--noise-seed", type=int, default=0, help="member m's noise seed is this + m")
@@ -122,6 +134,13 @@ def main(argv=None):
         ap.error("--share-replay takes 0 to --batch rows")
     if share and args.replay != "population":
         ap.error("--share-replay draws from the one arena of --replay population")
+    if args.prioritized is not None:
+        if args.replay != "population":
+            ap.error("--prioritized keeps its priorities beside the one arena of --replay population")
+        if args.share_replay is not None:
+            ap.error("--prioritized samples a member's own rows: it excludes --share-replay")
+        if not 0 <= args.prioritized < float("inf"):
+            ap.error("--prioritized takes a finite ALPHA >= 0")
     P, N = args.members, args.envs_per_member
     if N < 64 or N % 64:
         raise SystemExit("--envs-per-member must be a multiple of 64 (the act kernel's row block)")
@@ -132,7 +151,11 @@ def main(argv=None):
     configs = sample_hpsets(P, args.seed, base=AgentConfig(batch_size=args.batch))
     pooled = args.replay == "population"
     replay = None
-    if pooled:  # the members' buffers in one arena, with the seeds the per-member buffers get
+    if args.prioritized is not None:
+        from sacenv import PrioritizedPopulationReplay
+        replay = PrioritizedPopulationReplay(P, configs[0].max_size, (11,), 1, device=dev, seeds=list(range(P)),
+                                             alpha=args.prioritized)
+    elif pooled:  # the members' buffers in one arena, with the seeds the per-member buffers get
         replay = PopulationReplay(P, configs[0].max_size, (11,), 1, device=dev, seeds=list(range(P)))
     pop = NativeSACPopulation(dev, configs, init_seeds=list(range(P)), buffer_seeds=list(range(P)), replay=replay,
                               pool_rows=share,
@@ -252,6 +275,9 @@ def main(argv=None):
            "losses": None if losses is None else losses.tolist(), "table": table}
     if args.share_replay is not None:
         out.update(pool_rows=share)
+    if args.prioritized is not None:
+        out.update(prioritized={"alpha": replay.alpha, "beta": replay.beta, "eps": replay.eps,
+                                "totals": [replay.total(m) for m in range(P)]})
     if board is not None:
         out.update(device_table=device_table, kept=kept, best_member=board.best_member())
     if selection is not None:

@@ -20,10 +20,14 @@
 //
 // The pooled sample (include/sacenv_population_share.h) lives here too: two
 // kernels of their own, k_rb_draw_pool and k_rb_gather_pool, after the five above.
+//
+// The prioritized sample (include/sacenv_prioritized_replay.h) has its entry points
+// at the end; its device code is sacenv_replay_prio.h, and its gather is k_rb_gather_pop above.
 #include "sacenv_replay_core.h"
 
 #include "sacenv_population_replay.h"
 #include "sacenv_population_share.h"
+#include "sacenv_replay_prio.h"
 
 namespace {
 
@@ -404,4 +408,190 @@ extern "C" int sacenv_replay_pop_gather_pool(const SacenvReplayParams* p, int32_
   if (batch == 0) return SACENV_OK;
   return gather_pool(p, members, make_rb(*p, arena), batch, idx, state, action, reward, new_state, terminal,
                      stream);
+}
+
+// ---- include/sacenv_prioritized_replay.h
+
+namespace {
+
+// grid (blocks, P)
+__global__ void __launch_bounds__(256) k_prio_init(PT t) { prio_init_body(t, prio_slab(t, blockIdx.y)); }
+
+// member m's count before the store: the host's, or the one in its arena
+__device__ __forceinline__ int64_t prio_c0(const RB& r, int64_t member_bytes, int64_t host_cntr) {
+  return host_cntr >= 0 ? host_cntr : *member_rb(r, member_bytes, blockIdx.y).cntr();
+}
+
+// grid (blocks, P)
+__global__ void __launch_bounds__(256) k_prio_mark(PT t, RB r, int64_t member_bytes, int64_t host_cntr, int64_t n) {
+  prio_mark_body(t, prio_slab(t, blockIdx.y), prio_c0(r, member_bytes, host_cntr), n);
+}
+
+// grid (ceil(W / 4), P)
+__global__ void __launch_bounds__(kPrioThreads) k_prio_l1_span(PT t, RB r, int64_t member_bytes, int64_t host_cntr,
+                                                               int64_t n) {
+  prio_l1_span_body(t, prio_slab(t, blockIdx.y), prio_c0(r, member_bytes, host_cntr), n);
+}
+
+// grid (ceil(batch / 4), P)
+__global__ void __launch_bounds__(kPrioThreads) k_prio_l1_idx(PT t, int batch, const int64_t* __restrict__ idx) {
+  prio_l1_idx_body(t, prio_slab(t, blockIdx.y), batch, idx + (int64_t)blockIdx.y * batch);
+}
+
+// grid (1, P)
+__global__ void __launch_bounds__(kPrioMemberThreads) k_prio_upper(PT t) {
+  prio_upper_body(t, prio_slab(t, blockIdx.y));
+}
+
+// grid (1, P)
+template <bool kTd>
+__global__ void __launch_bounds__(kPrioMemberThreads) k_prio_write(PT t, int batch, const int64_t* __restrict__ idx,
+                                                                    const uint32_t* __restrict__ leaf, PrioTd td,
+                                                                    int64_t member_stride) {
+  const int64_t m = blockIdx.y;
+  PrioTd tm = td;
+  if (kTd) {
+    tm.sq1 = td.sq1 + m * member_stride;
+    tm.sq2 = td.sq2 != nullptr ? td.sq2 + m * member_stride : nullptr;
+  }
+  prio_write_body<kTd>(t, prio_slab(t, m), batch, idx + m * batch, kTd ? nullptr : leaf + m * batch, tm);
+}
+
+// grid (ceil(batch / 4), P)
+__global__ void __launch_bounds__(kPrioThreads) k_prio_draw(PT t, int batch, int64_t call, PrioSeeds seeds,
+                                                            int64_t* __restrict__ idx,
+                                                            uint32_t* __restrict__ leaf_out) {
+  const int64_t m = blockIdx.y;
+  prio_draw_body(t, prio_slab(t, m), (uint32_t)m, batch, call, seeds.v[m], idx + m * batch, leaf_out + m * batch);
+}
+
+// grid (1, P)
+__global__ void __launch_bounds__(kPrioMemberThreads) k_prio_finish(PT t, int batch, const uint32_t* __restrict__ leaf_out,
+                                                              float* __restrict__ weights, double beta, int advance) {
+  const int64_t m = blockIdx.y;
+  prio_finish_body(prio_slab(t, m), batch, leaf_out + m * batch, weights != nullptr ? weights + m * batch : nullptr,
+                   beta, advance != 0);
+}
+
+bool finite_nonneg(double x) { return x >= 0.0 && x <= 1.7976931348623157e308; }  // (false for NaN)
+
+// levels >= 2 and the total, after the leaves and level 1 are in place
+int prio_repair_upper(const PT& t, int32_t members, void* stream) {
+  hipLaunchKernelGGL(k_prio_upper, dim3(1, members), dim3(kPrioMemberThreads), 0, (hipStream_t)stream, t);
+  return status();
+}
+
+// the launches of sacenv_replay_prio_set and sacenv_replay_prio_update_td
+template <bool kTd>
+int prio_write(const SacenvReplayParams* p, int32_t members, void* state, int32_t batch, const int64_t* idx,
+               const uint32_t* leaf, const PrioTd& td, int64_t member_stride, void* stream) {
+  const PT t = make_pt(*p, state);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_prio_write<kTd>, dim3(1, members), dim3(kPrioMemberThreads), 0, s, t, (int)batch, idx, leaf, td,
+                     member_stride);
+  if (t.levels >= 2) {
+    const unsigned blocks = (unsigned)(((int64_t)batch + 3) / 4);
+    hipLaunchKernelGGL(k_prio_l1_idx, dim3(blocks, members), dim3(kPrioThreads), 0, s, t, (int)batch, idx);
+  }
+  const int rc = status();
+  return rc ? rc : prio_repair_upper(t, members, stream);
+}
+
+}  // namespace
+
+extern "C" int sacenv_replay_prio_layout(const SacenvReplayParams* p, int32_t members, SacenvReplayPrioLayout* out) {
+  const int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (out == nullptr) return SACENV_E_NULL;
+  prio_layout(p->mem_size, out);
+  out->total_bytes = members * out->member_bytes;
+  return SACENV_OK;
+}
+
+extern "C" int sacenv_replay_prio_init(const SacenvReplayParams* p, int32_t members, void* state, void* stream) {
+  const int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (state == nullptr) return SACENV_E_NULL;
+  if (!aligned256(state)) return SACENV_E_SIZE;
+  const PT t = make_pt(*p, state);
+  int64_t blocks = (t.member_bytes / 16 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(k_prio_init, dim3((unsigned)blocks, members), dim3(256), 0, (hipStream_t)stream, t);
+  return status();
+}
+
+extern "C" int sacenv_replay_prio_mark_stored(const SacenvReplayParams* p, int32_t members, const void* arena,
+                                              void* state, int64_t cntr, int64_t n, void* stream) {
+  int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (cntr < -1) return SACENV_E_RANGE;
+  if (n < 0) return SACENV_E_SIZE;
+  if (n == 0) return SACENV_OK;
+  if (state == nullptr || (cntr < 0 && arena == nullptr)) return SACENV_E_NULL;
+  if (!aligned256(state) || (cntr < 0 && !aligned256(arena))) return SACENV_E_SIZE;
+  const PT t = make_pt(*p, state);
+  const RB r = make_rb(*p, const_cast<void*>(arena));  // (read only, and only with cntr == -1)
+  const int64_t rows = n > p->mem_size ? p->mem_size : n;
+  int64_t blocks = (rows + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_prio_mark, dim3((unsigned)blocks, members), dim3(256), 0, s, t, r, r.L.total_bytes, cntr, n);
+  if (t.levels >= 2) {
+    int64_t waves = rows / kPrioFan + 3;  // the span's level-1 nodes: at most this many, and count[1] + 1
+    if (waves > t.count[1] + 1) waves = t.count[1] + 1;
+    hipLaunchKernelGGL(k_prio_l1_span, dim3((unsigned)((waves + 3) / 4), members), dim3(kPrioThreads), 0, s, t, r,
+                       r.L.total_bytes, cntr, n);
+  }
+  if ((rc = status())) return rc;
+  return prio_repair_upper(t, members, stream);
+}
+
+extern "C" int sacenv_replay_prio_set(const SacenvReplayParams* p, int32_t members, void* state, int32_t batch,
+                                      const int64_t* idx, const uint32_t* leaf, void* stream) {
+  const int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (batch < 0) return SACENV_E_SIZE;
+  if (batch == 0) return SACENV_OK;
+  if (state == nullptr || idx == nullptr || leaf == nullptr) return SACENV_E_NULL;
+  if (!aligned256(state)) return SACENV_E_SIZE;
+  return prio_write<false>(p, members, state, batch, idx, leaf, PrioTd{nullptr, nullptr, 0.0, 0.0}, 0, stream);
+}
+
+extern "C" int sacenv_replay_prio_update_td(const SacenvReplayParams* p, int32_t members, void* state, int32_t batch,
+                                            const int64_t* idx, const float* td_sq1, const float* td_sq2,
+                                            int64_t member_stride, double alpha, double eps, void* stream) {
+  const int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (batch < 0 || member_stride < 0) return SACENV_E_SIZE;
+  if (!finite_nonneg(alpha) || !finite_nonneg(eps)) return SACENV_E_RANGE;
+  if (batch == 0) return SACENV_OK;
+  if (state == nullptr || idx == nullptr || td_sq1 == nullptr) return SACENV_E_NULL;
+  if (!aligned256(state)) return SACENV_E_SIZE;
+  return prio_write<true>(p, members, state, batch, idx, nullptr, PrioTd{td_sq1, td_sq2, alpha, eps}, member_stride,
+                          stream);
+}
+
+extern "C" int sacenv_replay_prio_sample(const SacenvReplayParams* p, int32_t members, void* arena, void* state,
+                                         int32_t batch, int64_t call, const uint64_t* seeds, int64_t* idx,
+                                         uint32_t* leaf_out, float* weights, double beta, float* st, float* action,
+                                         double* reward, float* new_state, uint8_t* terminal, void* stream) {
+  int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (batch < 0) return SACENV_E_SIZE;
+  if (call < -1 || !finite_nonneg(beta)) return SACENV_E_RANGE;
+  if (batch == 0) return SACENV_OK;
+  if (arena == nullptr || state == nullptr || seeds == nullptr || idx == nullptr || leaf_out == nullptr)
+    return SACENV_E_NULL;
+  if (!aligned256(arena) || !aligned256(state) || batch_elems(p, batch) >= (1LL << 32)) return SACENV_E_SIZE;
+  const PT t = make_pt(*p, state);
+  PrioSeeds sd{};
+  for (int m = 0; m < members; ++m) sd.v[m] = seeds[m];
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_prio_draw, dim3((unsigned)(((int64_t)batch + 3) / 4), members), dim3(kPrioThreads), 0, s, t,
+                     (int)batch, call, sd, idx, leaf_out);
+  if (weights != nullptr || call < 0)
+    hipLaunchKernelGGL(k_prio_finish, dim3(1, members), dim3(kPrioMemberThreads), 0, s, t, (int)batch, leaf_out, weights,
+                       beta, call < 0 ? 1 : 0);
+  if ((rc = status())) return rc;
+  return sacenv_replay_pop_gather(p, members, arena, batch, idx, st, action, reward, new_state, terminal, stream);
 }

@@ -1151,6 +1151,9 @@ void set_member(SacArgs& a, const PopMember& m) {
 // The learn() arguments every agent of a call shares: the scratch partition and
 // Adam's scalars (torch.optim.Adam: Python-float scalars, cast to f32 in the
 // kernels). Returns bias_correction1 = 1 - beta1^step.
+// where the row fields start in one agent's learn scratch, in floats: after the 16 [kH][B] tiles
+inline int64_t learn_rows_offset(const SacenvSacParams* p) { return 16 * (int64_t)kH * p->batch; }
+
 double set_learn_common(SacArgs& a, const SacenvSacParams* p, void* scratch, int32_t adam_step) {
   float* scr = static_cast<float*>(scratch);
   const int64_t tile = (int64_t)kH * p->batch;
@@ -1160,7 +1163,7 @@ double set_learn_common(SacArgs& a, const SacenvSacParams* p, void* scratch, int
     a.na[t].dz1t = scr + (4 * t + 2) * tile;
     a.na[t].dz2t = scr + (4 * t + 3) * tile;
   }
-  a.rows = scr + 16 * tile;
+  a.rows = scr + learn_rows_offset(p);
   a.xt = a.rows + (int64_t)F_COUNT * p->batch;
   a.stamps = reinterpret_cast<unsigned long long*>(a.xt + 16 * (int64_t)p->batch);
   const double b1 = p->adam_beta1, b2 = p->adam_beta2;

@@ -24,6 +24,8 @@
 #include "sacenv_sac_core.h"
 #pragma clang attribute pop
 
+#include "sacenv_prioritized_replay.h"   // (its one accessor of the learn scratch lives here, at the end)
+
 namespace {
 
 constexpr int kPopMax = SACENV_SAC_POP_MAX_MEMBERS;
@@ -255,4 +257,16 @@ extern "C" int sacenv_sac_pop_learn(const SacenvSacParams* p, int32_t members, c
   hipLaunchKernelGGL(k_sac_rows_pop, dim3(4 * nrb, members), dim3(kThreads), 0, s, a, q, 2);
   hipLaunchKernelGGL(k_sac_update_pop, dim3(kUpdateBlocksPop, members), dim3(kThreads), 0, s, a, q);
   return (int)hipGetLastError();
+}
+
+// ---- include/sacenv_prioritized_replay.h: where role_critic_loss leaves (q - q_hat)^2 per batch
+// row (F_LC1, F_LC2 of the one RowField enum), as float offsets into one member's learn scratch
+extern "C" int sacenv_replay_prio_learn_rows(const SacenvSacParams* sp, int64_t* td_sq1_off, int64_t* td_sq2_off) {
+  const int rc = check(sp);
+  if (rc != SACENV_OK) return rc;
+  if (td_sq1_off == nullptr || td_sq2_off == nullptr) return SACENV_E_NULL;
+  const int64_t rows = learn_rows_offset(sp);
+  *td_sq1_off = rows + (int64_t)F_LC1 * sp->batch;  // rowf()
+  *td_sq2_off = rows + (int64_t)F_LC2 * sp->batch;
+  return SACENV_OK;
 }

@@ -10,7 +10,8 @@ from .spaces import Box
 
 __all__ = ["BoatConfig", "Box", "VecBoatEnv", "BoatEnv", "ParachuteEnv", "CarEnv", "VecToyEnv",
            "MixedBatch", "NativeSACPopulation", "sample_hpsets", "HPRanges", "PopulationReplay", "PolicyNoise",
-           "MemberScoreboard", "PopulationSelection", "BestEpisodes", "EpisodeFrames", "_lib"]
+           "MemberScoreboard", "PopulationSelection", "BestEpisodes", "EpisodeFrames",
+           "PrioritizedPopulationReplay", "_lib"]
 
 
 def __getattr__(name):  # lazy: importing torch-dependent classes only when used
@@ -29,6 +30,9 @@ def __getattr__(name):  # lazy: importing torch-dependent classes only when used
     if name == "PopulationReplay":
         from .population_replay import PopulationReplay
         return PopulationReplay
+    if name == "PrioritizedPopulationReplay":
+        from .prioritized import PrioritizedPopulationReplay
+        return PrioritizedPopulationReplay
     if name == "PolicyNoise":
         from .noise import PolicyNoise
         return PolicyNoise

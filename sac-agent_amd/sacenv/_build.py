@@ -23,10 +23,10 @@ SOURCES = ("sacenv_boat.hip", "sacenv_replay.hip", "sacenv_sac.hip", "sacenv_epi
 HEADERS = ("mt19937.h", "sacenv_replay_core.h", "sacenv_sac_core.h", "sacenv_philox.h",
            "sacenv_boat_arena.h", "sacenv_boat_math.h", "sacenv_boat_wind.h", "sacenv_boat_draw.h",
            "sacenv_toys.h", "sacenv_boat_owner.h", "sacenv_board_core.h", "sacenv_wave_core.h",
-           "sacenv_traces_frames.h")
+           "sacenv_traces_frames.h", "sacenv_replay_prio.h")
 PUBLIC_HEADERS = ("sacenv.h", "sacenv_episodes.h", "sacenv_population.h", "sacenv_population_replay.h",
                   "sacenv_noise.h", "sacenv_scoreboard.h", "sacenv_selection.h", "sacenv_traces.h",
-                  "sacenv_frames.h", "sacenv_population_share.h")
+                  "sacenv_frames.h", "sacenv_population_share.h", "sacenv_prioritized_replay.h")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fPIC", "-shared", "-Wall")
 

@@ -321,6 +321,26 @@ REPLAY_SHARE_VERSION = 1
 REPLAY_SHARE_EXPORTS = ("sacenv_replay_pop_sample_pool", "sacenv_replay_pop_gather_pool")
 
 
+# include/sacenv_prioritized_replay.h (SACENV_REPLAY_PRIO_VERSION 1): per-member sum trees over the
+# ring rows' priorities, marked, updated and sampled on the device; beside the ABI of sacenv.h,
+# bound only where the library has them
+REPLAY_PRIO_VERSION = 1
+REPLAY_PRIO_MAX_LEVELS = 6
+REPLAY_PRIO_HEADER_BYTES = 256
+REPLAY_PRIO_ONE = 65536
+REPLAY_PRIO_MAX_LEAF = 0x7FFFFFFF
+REPLAY_PRIO_KEY1 = 0x7072696F
+REPLAY_PRIO_EXPORTS = ("sacenv_replay_prio_layout", "sacenv_replay_prio_init", "sacenv_replay_prio_mark_stored",
+                       "sacenv_replay_prio_set", "sacenv_replay_prio_update_td", "sacenv_replay_prio_learn_rows",
+                       "sacenv_replay_prio_sample")
+
+
+class ReplayPrioLayout(C.Structure):
+    """SacenvReplayPrioLayout (sacenv_prioritized_replay.h)."""
+    _fields_ = [("member_bytes", _i64), ("total_bytes", _i64), ("levels", _i32), ("pad", _i32),
+                ("count", _i64 * REPLAY_PRIO_MAX_LEVELS), ("offset", _i64 * REPLAY_PRIO_MAX_LEVELS)]
+
+
 class Frames(C.Structure):
     """SacenvFrames (sacenv_frames.h)."""
     _fields_ = [("width", _i32), ("height", _i32), ("strip", _i32), ("members", _i32), ("max_steps", _i32),
@@ -444,7 +464,12 @@ def load(path: str | None = None):
         (FRAMES_EXPORTS, ([C.POINTER(Frames), C.POINTER(_i64), C.POINTER(_i64)],
                           [C.POINTER(Frames), _p, _i32, _i64, _i32, _i32, _p, _p, _p])),
         (REPLAY_SHARE_EXPORTS, ([RP, _i32, _p, _i32, _i32, _i64, _p, _p, _p, _p, _p, _p, _p],
-                                [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])))
+                                [RP, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p])),
+        (REPLAY_PRIO_EXPORTS, (
+            [RP, _i32, C.POINTER(ReplayPrioLayout)], [RP, _i32, _p, _p], [RP, _i32, _p, _p, _i64, _i64, _p],
+            [RP, _i32, _p, _i32, _p, _p, _p], [RP, _i32, _p, _i32, _p, _p, _p, _i64, _d, _d, _p],
+            [QP, C.POINTER(_i64), C.POINTER(_i64)],
+            [RP, _i32, _p, _p, _i32, _i64, C.POINTER(C.c_uint64), _p, _p, _p, _d, _p, _p, _p, _p, _p, _p])))
     for names, argtypes in optional:
         assert len(names) == len(argtypes)
         for name, args in zip(names, argtypes):
@@ -522,6 +547,13 @@ def sac_pop_layout(params: SacParams, members: int) -> SacPopLayout:
 def replay_pop_layout(params: ReplayParams, members: int) -> ReplayPopLayout:
     fn, = require(REPLAY_POP_EXPORTS[:1], "sacenv_population_replay.h")
     out = ReplayPopLayout()
+    check(fn(C.byref(params), int(members), C.byref(out)))
+    return out
+
+
+def replay_prio_layout(params: ReplayParams, members: int) -> ReplayPrioLayout:
+    fn, = require(REPLAY_PRIO_EXPORTS[:1], "sacenv_prioritized_replay.h")
+    out = ReplayPrioLayout()
     check(fn(C.byref(params), int(members), C.byref(out)))
     return out
 

@@ -108,7 +108,9 @@ class NativeSACPopulation(_SacCore):
     or a ``PopulationReplay`` given as ``replay=`` (two launches, no stacking) -- and returns
     [P, 4] losses. ``pool_rows=K`` (with ``replay=``): K of every member's B rows come from all
     members' rings (include/sacenv_population_share.h); a member still learns once its own ring
-    holds B rows, and with K > 0 its weights depend on the other members' rows."""
+    holds B rows, and with K > 0 its weights depend on the other members' rows. With a
+    ``PrioritizedPopulationReplay`` as ``replay=`` (sacenv/prioritized.py) a ``learn()`` that sampled
+    the replay itself hands the batch's TD errors back to it afterwards."""
 
     def __init__(self, device, configs, *, obs_dim: int = 11, max_action: float = 1.0, init_seeds=None,
                  buffer_seeds=None, with_memory: bool = True, adam_eps: float = 1e-8, replay=None,
@@ -155,6 +157,12 @@ class NativeSACPopulation(_SacCore):
             self.sync()
         self.memory = None
         self._pop_replay = replay is not None
+        # a PrioritizedPopulationReplay (sacenv/prioritized.py): learn() on its own sample hands the
+        # rows' TD errors back to it; with any other replay nothing changes
+        from .prioritized import PrioritizedPopulationReplay
+        self._prioritized = isinstance(replay, PrioritizedPopulationReplay)
+        if self._prioritized and self.pool_rows:
+            raise ValueError("a prioritized replay does not pool: pool_rows must be 0")
         if replay is not None:
             self.memory = replay
         elif with_memory:
@@ -194,6 +202,14 @@ class NativeSACPopulation(_SacCore):
         if mem is None or (mem.mem_cntr < B if self._pop_replay else any(b.mem_cntr < B for b in mem)):
             return None
         return self.sample()
+
+    def learn(self, batch=None, noise=None, *, losses: bool = True):
+        out = super().learn(batch, noise, losses=losses)
+        if self._prioritized and batch is None and out is not None:
+            self.memory.update_from_learn(self)   # the batch was the replay's last sample
+        return out
+
+    learn.__doc__ = _SacCore.learn.__doc__
 
     # ---- members in and out
 
