@@ -214,7 +214,7 @@ __global__ void __launch_bounds__(kTileThreads) k_draw_emit(DrawPlan d, RB r, in
   __shared__ int wc[kTileThreads / kWave];
   plan_start(d, n_blocks);
   __shared__ int64_t s_end;   // stream position after the last wanted word (this tile only)
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  const int tid = threadIdx.x;
   const int last = d.ctrl[0];
   if (last < 0) {  // too few words generated (never at the planned margin): report, draw nothing;
     // the stream position -1 marks the arena (StagedReplay.check raises)
@@ -234,17 +234,9 @@ __global__ void __launch_bounds__(kTileThreads) k_draw_emit(DrawPlan d, RB r, in
     bool acc = false;
     uint32_t w = 0u;
     if (t < d.n_words) w = plan_word(d, t, &acc);
-    const unsigned long long bal = __ballot(acc);
     __syncthreads();  // wc of the previous round read
-    if (lane == 0) wc[wv] = __popcll(bal);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < kTileThreads / kWave; ++i) {
-      before += i < wv ? wc[i] : 0;
-      total += wc[i];
-    }
-    const int64_t rank = (int64_t)run + before + __popcll(bal & ((1ull << lane) - 1ull));
+    int total;
+    const int64_t rank = (int64_t)run + block_rank<kTileThreads>(acc, wc, &total);
     if (acc && rank < d.need) idx[rank] = (int64_t)w;
     if (acc && rank == d.need - 1) s_end = d.p0 + t + 1;
     run += total;
@@ -298,6 +290,36 @@ struct StagedRows {
   float first[SACENV_OBS_DIM];
 };
 
+// The staged rows of one sampled transition, (global step q, global env u) on this rank (`own`;
+// else zeros, terminal 0): sn = the row itself (s', reward [11], action [12], codes [13]), sv
+// = the row before it (s), with the fresh-Boat obs where that step ended an episode
+// (first_obs; exp 2: with that row's obs3_next). Returns (terminal_mask >> last_term) & 1.
+__device__ __forceinline__ uint32_t staged_read(const SacenvReplayParams& p, const StagedGeom& G,
+                                                const StagedRows& S, bool own, int64_t q, int64_t u,
+                                                float (&sn)[16], float (&sv)[16]) {
+#pragma unroll
+  for (int k = 0; k < 16; ++k) sn[k] = sv[k] = 0.f;
+  if (!own) return 0u;
+  const int e = (int)(u - G.offset);
+  int64_t j = q - G.g * G.seg;  // > -seg (M <= seg * period)
+  const bool in_cur = j >= 0;
+  j = in_cur ? j : j + G.seg;
+  const float4* R = reinterpret_cast<const float4*>((in_cur ? S.cur : S.prev) + stage_row(G, e, j));
+  const float4* P = j > 0 ? R - 4 : reinterpret_cast<const float4*>(S.prev + stage_row(G, e, G.seg - 1));
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float4 x = R[k], y = P[k];
+    sn[4 * k] = x.x, sn[4 * k + 1] = x.y, sn[4 * k + 2] = x.z, sn[4 * k + 3] = x.w;
+    sv[4 * k] = y.x, sv[4 * k + 1] = y.y, sv[4 * k + 2] = y.z, sv[4 * k + 3] = y.w;
+  }
+  const bool pdone = (__float_as_uint(sv[13]) & 0xFFu) != 0u;
+  const float o3 = sv[14];
+#pragma unroll
+  for (int k = 0; k < SACENV_OBS_DIM; ++k) sv[k] = pdone ? S.first[k] : sv[k];
+  if (G.exp2 && pdone) sv[3] = o3;
+  return (p.terminal_mask >> ((__float_as_uint(sn[13]) >> 8) & 0xFFu)) & 1u;
+}
+
 // One thread per sampled row (batch b, row i): the ring row -> (step, global
 // env) at learn b; this rank's rows are read from the staged segments: s' =
 // the row's obs, s = the previous step's s' (or the fresh-Boat obs where that
@@ -319,29 +341,7 @@ __global__ void __launch_bounds__(256) k_rb_gather_staged(SacenvReplayParams p, 
   const bool own = u >= G.offset && u < G.offset + G.n;
   uint32_t* const W = words + (int64_t)b * per;
   float sn[16], sv[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) sn[k] = sv[k] = 0.f;
-  uint32_t tm = 0u;
-  if (own) {
-    const int e = (int)(u - G.offset);
-    int64_t j = q - G.g * G.seg;  // > -seg (M <= seg * period)
-    const bool in_cur = j >= 0;
-    j = in_cur ? j : j + G.seg;
-    const float4* R = reinterpret_cast<const float4*>((in_cur ? S.cur : S.prev) + stage_row(G, e, j));
-    const float4* P = j > 0 ? R - 4 : reinterpret_cast<const float4*>(S.prev + stage_row(G, e, G.seg - 1));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float4 x = R[k], y = P[k];
-      sn[4 * k] = x.x, sn[4 * k + 1] = x.y, sn[4 * k + 2] = x.z, sn[4 * k + 3] = x.w;
-      sv[4 * k] = y.x, sv[4 * k + 1] = y.y, sv[4 * k + 2] = y.z, sv[4 * k + 3] = y.w;
-    }
-    const bool pdone = (__float_as_uint(sv[13]) & 0xFFu) != 0u;
-    const float o3 = sv[14];
-#pragma unroll
-    for (int k = 0; k < D; ++k) sv[k] = pdone ? S.first[k] : sv[k];
-    if (G.exp2 && pdone) sv[3] = o3;
-    tm = (p.terminal_mask >> ((__float_as_uint(sn[13]) >> 8) & 0xFFu)) & 1u;
-  }
+  const uint32_t tm = staged_read(p, G, S, own, q, u, sn, sv);
   const double r64 = (double)sn[11];
   uint64_t rb;
   __builtin_memcpy(&rb, &r64, 8);
@@ -400,24 +400,6 @@ __host__ __device__ __forceinline__ uint64_t range_mask(uint64_t rng) {
 }
 
 constexpr int kPackTile = 256;
-
-// the tile's records before this thread's (the block's waves in order): returns the
-// exclusive rank, *tile_total the tile's count
-__device__ __forceinline__ int tile_rank(bool take, int* wcnt, int* tile_total) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  const unsigned long long bal = __ballot(take);
-  if (lane == 0) wcnt[wv] = __popcll(bal);
-  __syncthreads();
-  int before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kPackTile / kWave; ++w) {
-    const int c = wcnt[w];
-    before += w < wv ? c : 0;
-    total += c;
-  }
-  *tile_total = total;
-  return before + __popcll(bal & ((1ull << lane) - 1ull));
-}
 
 // The all-gather form of the exchange. Each rank packs the rows IT owns of the
 // segment's learns -- one 25-word record per sampled row: slot (learn x batch +
@@ -498,7 +480,7 @@ __device__ __forceinline__ void draw_ctr_tile(const SacenvReplayParams& p, const
   }
   if (tile_cnt != nullptr) {  // the pack's per-tile record counts, drawn ahead
     int tile_total;
-    tile_rank(take, wcnt, &tile_total);
+    block_rank<kPackTile>(take, wcnt, &tile_total);
     if (threadIdx.x == 0 && (int64_t)tile * kPackTile < total) tile_cnt[tile] = tile_total;
   }
 }
@@ -544,35 +526,12 @@ __device__ __forceinline__ void pack_tile(const SacenvReplayParams& p, const Sta
   const int64_t row = live ? idx[t] : -2;
   int64_t q = 0, u = -1;
   const bool take = live && pack_takes(p, G, batch, t, row, skip_owner, &q, &u);
-  const bool own = take && row >= 0;
   int tile_total;
-  const int rank = tile_rank(take, l.wcnt, &tile_total);  // (its barrier also publishes l.base)
+  const int rank = block_rank<kPackTile>(take, l.wcnt, &tile_total);  // (its barrier also publishes l.base)
   const int64_t base = l.base;
   if (tile == n_tiles - 1 && tid == 0) chunk[0] = (uint32_t)(base + tile_total);  // the record count
   float sn[16], sv[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) sn[k] = sv[k] = 0.f;
-  uint32_t tm = 0u;
-  if (own) {  // (as k_rb_gather_staged)
-    const int e = (int)(u - G.offset);
-    int64_t j = q - G.g * G.seg;
-    const bool in_cur = j >= 0;
-    j = in_cur ? j : j + G.seg;
-    const float4* R = reinterpret_cast<const float4*>((in_cur ? S.cur : S.prev) + stage_row(G, e, j));
-    const float4* P = j > 0 ? R - 4 : reinterpret_cast<const float4*>(S.prev + stage_row(G, e, G.seg - 1));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float4 x = R[k], y = P[k];
-      sn[4 * k] = x.x, sn[4 * k + 1] = x.y, sn[4 * k + 2] = x.z, sn[4 * k + 3] = x.w;
-      sv[4 * k] = y.x, sv[4 * k + 1] = y.y, sv[4 * k + 2] = y.z, sv[4 * k + 3] = y.w;
-    }
-    const bool pdone = (__float_as_uint(sv[13]) & 0xFFu) != 0u;
-    const float o3 = sv[14];
-#pragma unroll
-    for (int k = 0; k < D; ++k) sv[k] = pdone ? S.first[k] : sv[k];
-    if (G.exp2 && pdone) sv[3] = o3;
-    tm = (p.terminal_mask >> ((__float_as_uint(sn[13]) >> 8) & 0xFFu)) & 1u;
-  }
+  const uint32_t tm = staged_read(p, G, S, take && row >= 0, q, u, sn, sv);
   if (take) {
     uint32_t* const rec = l.rec + rank * kRecWords;
     rec[0] = (uint32_t)t | (tm << 31);
@@ -667,7 +626,7 @@ __global__ void __launch_bounds__(kPackTile) k_rb_pack_count(SacenvReplayParams 
   int64_t q, u;
   const bool take = t < (int64_t)batch * nb && pack_takes(p, G, batch, t, idx[t], skip_owner, &q, &u);
   int total;
-  tile_rank(take, wcnt, &total);
+  block_rank<kPackTile>(take, wcnt, &total);
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
 }
 

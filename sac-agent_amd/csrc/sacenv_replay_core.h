@@ -1,9 +1,10 @@
 // sacenv_replay_core.h — what the one-buffer unit (sacenv_replay.hip) and the population
 // unit (sacenv_replay_pop.hip) share: the constants, the arena layout, RB, the device
-// bodies of the five one-buffer kernels, the sharded and staged geometry, the MT19937
-// block twist, and the host rules both units apply (the parameter and call checks, the
-// store's and the gather's grid). No kernel and no entry point lives here: each unit
-// wraps the bodies in its own kernels.
+// bodies of the five one-buffer kernels, the sharded and staged geometry, the pieces every
+// draw and gather is built from (block_rank; draw_open / fill_masked / draw_close on the
+// MT19937 block twist; gather_split), and the host rules both units apply (the parameter
+// and call checks, the store's and the gather's grid). No kernel and no entry point lives
+// here: each unit wraps the bodies in its own kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -154,29 +155,59 @@ __device__ __forceinline__ bool owns(const Shard& sh, int64_t cnt, int64_t M, in
   return u >= sh.lo && u < sh.hi;
 }
 
+// The gather's column split, one thread per output element: thread q of the grid maps to
+// (state / new_state | action | reward + terminal, sampled row i, column k), and `at` resolves
+// idx[i] to a GatherRow -- the slab the row lies in, the row, and whether it is there at all (a
+// row that is not reads nothing: zero bits). Outputs are [..][batch][..] with this call's
+// rows from row out0 on; a null output is skipped.
+struct GatherRow {
+  RB rb;
+  int64_t row;
+  bool in;
+};
+template <class At>
+__device__ __forceinline__ void gather_split(const SacenvReplayParams& p, int batch, const int64_t* __restrict__ idx,
+                                             int64_t out0, float* __restrict__ st, float* __restrict__ ac,
+                                             double* __restrict__ rw, float* __restrict__ ns,
+                                             uint8_t* __restrict__ tm, const At& at) {
+  const int D = p.obs_dim, A = p.act_dim;
+  const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t nd = (int64_t)batch * D, na = (int64_t)batch * A;
+  int64_t i, k;
+  int part;
+  if (q < nd) {
+    i = q / D, k = q - i * D, part = 0;
+  } else if (q < nd + na) {
+    const int64_t qq = q - nd;
+    i = qq / A, k = qq - i * A, part = 1;
+  } else if (q < nd + na + batch) {
+    i = q - nd - na, k = 0, part = 2;
+  } else {
+    return;
+  }
+  const GatherRow g = at(idx[i]);
+  const int64_t row = g.row, o = out0 + i;
+  if (part == 0) {
+    if (st) st[o * D + k] = g.in ? g.rb.state()[row * D + k] : 0.f;
+    if (ns) ns[o * D + k] = g.in ? g.rb.new_state()[row * D + k] : 0.f;
+  } else if (part == 1) {
+    if (ac) ac[o * A + k] = g.in ? g.rb.action()[row * A + k] : 0.f;
+  } else {
+    if (rw) rw[o] = g.in ? g.rb.reward()[row] : 0.0;
+    if (tm) tm[o] = g.in ? g.rb.terminal()[row] : (uint8_t)0;
+  }
+}
+
+// one buffer's ring rows: a row of the ring that this shard wrote (an index outside the ring
+// -- a caller's, sacenv_replay_gather -- reads nothing)
 __device__ __forceinline__ void gather_body(const SacenvReplayParams& p, const RB& r, int batch,
                                             const int64_t* __restrict__ idx, float* __restrict__ st,
                                             float* __restrict__ ac, double* __restrict__ rw,
                                             float* __restrict__ ns, uint8_t* __restrict__ tm, const Shard& sh) {
-  const int D = p.obs_dim, A = p.act_dim;
-  const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t nd = (int64_t)batch * D, na = (int64_t)batch * A;
   const int64_t cnt = *r.cntr(), M = p.mem_size;
-  // (an index outside the ring -- a caller's, sacenv_replay_gather -- reads nothing: zero bits)
-  if (q < nd) {
-    const int64_t i = q / D, k = q - i * D, row = idx[i];
-    const bool own = row >= 0 && row < M && owns(sh, cnt, M, row);
-    if (st) st[q] = own ? r.state()[row * D + k] : 0.f;
-    if (ns) ns[q] = own ? r.new_state()[row * D + k] : 0.f;
-  } else if (q < nd + na) {
-    const int64_t qq = q - nd, i = qq / A, k = qq - i * A, row = idx[i];
-    if (ac) ac[qq] = row >= 0 && row < M && owns(sh, cnt, M, row) ? r.action()[row * A + k] : 0.f;
-  } else if (q < nd + na + batch) {
-    const int64_t i = q - nd - na, row = idx[i];
-    const bool own = row >= 0 && row < M && owns(sh, cnt, M, row);
-    if (rw) rw[i] = own ? r.reward()[row] : 0.0;
-    if (tm) tm[i] = own ? r.terminal()[row] : (uint8_t)0;
-  }
+  gather_split(p, batch, idx, 0, st, ac, rw, ns, tm, [&](int64_t row) {
+    return GatherRow{r, row, row >= 0 && row < M && owns(sh, cnt, M, row)};
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -229,14 +260,9 @@ __device__ __forceinline__ void resolve(int64_t row, int64_t cntr, int64_t M, co
   *u = s - *q * G.period;
 }
 
-// n_batches consecutive np.random.choice(min(cntr_k, M), batch) calls on one
-// stream, cntr_k = cntr0 + (k + 1) * period (learn k follows step k's stores),
-// learns with cntr_k < batch skipped (continuous_agent.py:97-98: idx = -1, no
-// words). The general path (ranges that change between learns): one workgroup;
-// a whole 624-word block is tempered and tested at once (thread i: word i),
-// accepted words are ranked with a ballot per wave and a prefix over the
-// waves; a batch that completes inside the block ends at its last accepted
-// word, and the next batch re-tests the block from there.
+// The draws walk one MT19937 stream per buffer with one 1 024-thread workgroup: a whole
+// 624-word block is tempered and tested at once (thread i: word i), and accepted words are
+// ranked with a ballot per wave and a prefix over the waves.
 constexpr int kDrawThreads = 1024;
 __device__ __forceinline__ void mt_twist_block(const uint32_t* __restrict__ o, uint32_t* __restrict__ n, int tid) {
   constexpr int kD = kMtN - kMtM;  // 227
@@ -250,79 +276,128 @@ __device__ __forceinline__ void mt_twist_block(const uint32_t* __restrict__ o, u
   __syncthreads();
 }
 
-// kSample: one sample_buffer(batch) at the device count (sacenv_replay_sample: no
-// learn() skip below batch rows; graph-capturable like the store), else the nb
-// learns of a staged segment at counts cntr0 + (k + 1) * period.
-template <bool kSample>
-__device__ __forceinline__ void draw_many_body(const SacenvReplayParams& p, const RB& r, int batch, int nb,
-                                               int64_t cntr0, int64_t period, int64_t* __restrict__ idx) {
+// The taking threads of a kThreads-thread workgroup before this one, its waves in order:
+// returns the exclusive rank, *total the workgroup's count. One barrier; wcnt (LDS
+// [kThreads / kWave]) is free again after the caller's next barrier.
+template <int kThreads>
+__device__ __forceinline__ int block_rank(bool take, int* wcnt, int* total) {
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  const unsigned long long bal = __ballot(take);
+  if (lane == 0) wcnt[wv] = __popcll(bal);
+  __syncthreads();
+  int before = 0, sum = 0;
+#pragma unroll
+  for (int w = 0; w < kThreads / kWave; ++w) {
+    const int c = wcnt[w];
+    before += w < wv ? c : 0;
+    sum += c;
+  }
+  *total = sum;
+  return before + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// A workgroup's view of one buffer's stream while it draws: the key block pair in LDS, the
+// position of the next word in blk[cur], and whether blk[cur] is no longer the arena's key.
+struct DrawBlock {
+  uint32_t (*blk)[kMtN];  // LDS [2][kMtN]
+  int* wcnt;              // LDS [kDrawThreads / kWave]
+  int* s_end;             // LDS
+  int cur, pos;
+  bool advanced;
+};
+
+// Opens r's stream on the workgroup's LDS (one stream per workgroup): false for a poisoned
+// stream (a staged draw ran short: the caller draws nothing, and the poison stays).
+__device__ __forceinline__ bool draw_open(DrawBlock& d, const RB& r) {
   __shared__ uint32_t blk[2][kMtN];
   __shared__ int wcnt[kDrawThreads / kWave];
   __shared__ int s_end;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  constexpr int kWaves = kDrawThreads / kWave;
-  int cur = 0, pos = *r.pos();
-  if (pos < 0) {  // a poisoned stream (a staged draw ran short): draw nothing, keep the poison
+  d = DrawBlock{blk, wcnt, &s_end, 0, *r.pos(), false};
+  if (d.pos < 0) return false;
+  for (int i = threadIdx.x; i < kMtN; i += kDrawThreads) blk[0][i] = r.key()[i];
+  __syncthreads();
+  return true;
+}
+
+// the stream's state after the draws: the key if a fill twisted it, and the position
+__device__ __forceinline__ void draw_close(const DrawBlock& d, const RB& r) {
+  if (d.advanced)
+    for (int i = threadIdx.x; i < kMtN; i += kDrawThreads) r.key()[i] = d.blk[d.cur][i];
+  if (threadIdx.x == 0) *r.pos() = d.pos;
+}
+
+// One masked-rejection fill: `count` accepted words (w & mask <= rng, rng >= 1) from position
+// d.pos on, in order, to put(0 .. count - 1, w); the stream stops after the last accepted word
+// (the word 623 of a block leaves pos = 624: the next fill twists first). A block that holds
+// fewer than the words still wanted is taken whole and the next one twisted. Every thread of
+// the workgroup calls it with the same arguments, and fills with different ranges and counts
+// run back to back on one stream.
+// Two barriers a round -- block_rank's, and one after s_end is written and wcnt read -- and a
+// third in the round that ends the fill, after s_end is read. The third is not needed for
+// the LDS traffic: whoever writes s_end next (the next fill's first round) does so behind
+// that round's block_rank barrier, which no thread passes before every thread has read s_end
+// here, and wcnt's next writer is behind the second barrier, as in every round. It stays
+// because without it the compiler peels the first round out of the loop (each fill's code
+// x 1.4).
+template <class Put>
+__device__ __forceinline__ void fill_masked(DrawBlock& d, uint32_t rng, int count, const Put& put) {
+  const int tid = threadIdx.x;
+  const uint32_t mask = range_mask32(rng);
+  int filled = 0;
+  for (;;) {
+    if (d.pos >= kMtN) {
+      mt_twist_block(d.blk[d.cur], d.blk[d.cur ^ 1], tid);
+      d.cur ^= 1;
+      d.pos = 0;
+      d.advanced = true;
+    }
+    const bool valid = tid >= d.pos && tid < kMtN;
+    const uint32_t w = valid ? (mt_temper(d.blk[d.cur][tid]) & mask) : 0u;
+    const bool acc = valid && w <= rng;
+    int total;
+    const int rank = block_rank<kDrawThreads>(acc, d.wcnt, &total);
+    const int take = count - filled;
+    if (acc && rank < take) put(filled + rank, w);
+    const bool done = total >= take;  // the take-th accepted word ends the fill
+    if (done && acc && rank == take - 1) *d.s_end = tid;
+    __syncthreads();
+    if (done) {
+      d.pos = *d.s_end + 1;
+      __syncthreads();  // (see above)
+      return;
+    }
+    filled += total;
+    d.pos = kMtN;
+  }
+}
+
+// n_batches consecutive np.random.choice(min(cntr_k, M), batch) calls on one stream, one fill
+// each. kSample: one sample_buffer(batch) at the device count (sacenv_replay_sample: no
+// learn() skip below batch rows; graph-capturable like the store), else the nb learns of a
+// staged segment at counts cntr_k = cntr0 + (k + 1) * period (learn k follows step k's
+// stores), learns with cntr_k < batch skipped (continuous_agent.py:97-98: idx = -1, no words).
+template <bool kSample>
+__device__ __forceinline__ void draw_many_body(const SacenvReplayParams& p, const RB& r, int batch, int nb,
+                                               int64_t cntr0, int64_t period, int64_t* __restrict__ idx) {
+  const int tid = threadIdx.x;
+  DrawBlock d;
+  if (!draw_open(d, r)) {
     for (int64_t i = tid; i < (int64_t)nb * batch; i += kDrawThreads) idx[i] = -1;
     return;
   }
-  for (int i = tid; i < kMtN; i += kDrawThreads) blk[0][i] = r.key()[i];
-  bool advanced = false;
-  __syncthreads();
-  int k = 0, filled = 0;
-  while (k < nb) {
+  for (int k = 0; k < nb; ++k) {
     const int64_t c = kSample ? *r.cntr() : cntr0 + (int64_t)(k + 1) * period;
     const int64_t max_mem = c < p.mem_size ? c : p.mem_size;
     const uint32_t rng = (uint32_t)(max_mem - 1);
     const bool skip = !kSample && c < batch;
+    int64_t* const out = idx + (int64_t)k * batch;
     if (skip || rng == 0u) {  // learn() returns before sampling, or numpy's off + 0: no words
-      for (int i = tid; i < batch; i += kDrawThreads) idx[(int64_t)k * batch + i] = skip ? -1 : 0;
-      ++k;
+      for (int i = tid; i < batch; i += kDrawThreads) out[i] = skip ? -1 : 0;
       continue;
     }
-    uint32_t mask = rng;
-    mask |= mask >> 1;
-    mask |= mask >> 2;
-    mask |= mask >> 4;
-    mask |= mask >> 8;
-    mask |= mask >> 16;
-    if (pos >= kMtN) {
-      mt_twist_block(blk[cur], blk[cur ^ 1], tid);
-      cur ^= 1;
-      pos = 0;
-      advanced = true;
-    }
-    const bool valid = tid >= pos && tid < kMtN;
-    const uint32_t w = valid ? (mt_temper(blk[cur][tid]) & mask) : 0u;
-    const bool acc = valid && w <= rng;
-    const unsigned long long bal = __ballot(acc);
-    if (lane == 0) wcnt[wv] = __popcll(bal);
-    __syncthreads();
-    int excl = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < kWaves; ++q) {
-      const int v = wcnt[q];
-      excl += q < wv ? v : 0;
-      total += v;
-    }
-    const int rank = excl + __popcll(bal & ((1ull << lane) - 1ull));
-    const int take = batch - filled;
-    if (acc && rank < take) idx[(int64_t)k * batch + filled + rank] = (int64_t)w;
-    if (total >= take) {  // the take-th accepted word ends batch k
-      if (acc && rank == take - 1) s_end = tid;
-      __syncthreads();
-      pos = s_end + 1;
-      ++k;
-      filled = 0;
-    } else {
-      filled += total;
-      pos = kMtN;
-    }
-    __syncthreads();  // wcnt / s_end are rewritten by the next round
+    fill_masked(d, rng, batch, [&](int i, uint32_t w) { out[i] = (int64_t)w; });
   }
-  if (advanced)
-    for (int i = tid; i < kMtN; i += kDrawThreads) r.key()[i] = blk[cur][i];
-  if (tid == 0) *r.pos() = pos;
+  draw_close(d, r);
 }
 
 int check_replay(const SacenvReplayParams* p) {

@@ -12,11 +12,14 @@
 // per-member table, the seeds of the init launch, is read from the kernel arguments
 // with scalar loads at an SGPR offset, as PopArgs is in sacenv_sac_pop.hip.
 //
-// This is a translation unit of its own, which shares the device bodies and the host
-// rules with sacenv_replay.hip through sacenv_replay_core.h: the one-buffer kernels, and
-// above all the staged, side and stand-in kernels of the timed replay path, are compiled
-// where they were, alone (tools/kernel_diff.py; DESIGN.md §4.6.1 has the result and the
-// resource table).
+// Every draw and gather of both units is built from one set of pieces in
+// sacenv_replay_core.h: draw_open / fill_masked / draw_close -- the
+// stream in LDS, numpy's masked-rejection round, the write-back -- under block_rank, and
+// gather_split, the column split and the five stores over a resolver from an index to
+// (slab, row, valid). This is a translation unit of its own all the same: the one-buffer
+// kernels, and above all the staged, side and stand-in kernels of the timed replay path,
+// are compiled where they were, alone (tools/kernel_diff.py; DESIGN.md §4.6.1 has the
+// result and the resource table).
 //
 // The pooled sample (include/sacenv_population_share.h) lives here too: two
 // kernels of their own, k_rb_draw_pool and k_rb_gather_pool, after the five above.
@@ -91,86 +94,19 @@ __global__ void __launch_bounds__(256) k_rb_gather_pop(SacenvReplayParams p, RB 
 // ---------------------------------------------------------------------------
 // The pooled sample (include/sacenv_population_share.h): member m draws B - K rows of its own
 // ring and K rows of the whole arena from its own stream, and the gather reads each row from
-// its owner's slab. Both kernels are new bodies: draw_many_body and gather_body, and every
-// kernel above, are as they were.
-
-// One masked-rejection fill on the workgroup's key block: `count` accepted words (w & mask <=
-// rng, rng >= 1) from position `pos` on, in order, to out[0, count) through `put`; the stream
-// stops after the last accepted word. The round of draw_many_body -- a whole 624-word block
-// tempered and tested at once, thread i word i, accepted words ranked by a ballot per wave and
-// a prefix over the waves -- as a loop of its own, so that two fills with different ranges and
-// counts run back to back on one block pair. Every thread of the workgroup calls it with the
-// same arguments.
-struct DrawBlock {
-  uint32_t (*blk)[kMtN];  // LDS [2][kMtN]
-  int* wcnt;              // LDS [kDrawThreads / kWave]
-  int* s_end;             // LDS
-  int cur, pos;
-  bool advanced;
-};
-
-template <class Put>
-__device__ __forceinline__ void fill_masked(DrawBlock& d, uint32_t rng, int count, const Put& put) {
-  constexpr int kWaves = kDrawThreads / kWave;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-  uint32_t mask = rng;
-  mask |= mask >> 1;
-  mask |= mask >> 2;
-  mask |= mask >> 4;
-  mask |= mask >> 8;
-  mask |= mask >> 16;
-  int filled = 0;
-  for (;;) {
-    if (d.pos >= kMtN) {
-      mt_twist_block(d.blk[d.cur], d.blk[d.cur ^ 1], tid);
-      d.cur ^= 1;
-      d.pos = 0;
-      d.advanced = true;
-    }
-    const bool valid = tid >= d.pos && tid < kMtN;
-    const uint32_t w = valid ? (mt_temper(d.blk[d.cur][tid]) & mask) : 0u;
-    const bool acc = valid && w <= rng;
-    const unsigned long long bal = __ballot(acc);
-    if (lane == 0) d.wcnt[wv] = __popcll(bal);
-    __syncthreads();
-    int excl = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < kWaves; ++q) {
-      const int v = d.wcnt[q];
-      excl += q < wv ? v : 0;
-      total += v;
-    }
-    const int rank = excl + __popcll(bal & ((1ull << lane) - 1ull));
-    const int take = count - filled;
-    if (acc && rank < take) put(filled + rank, w);
-    const bool done = total >= take;  // the take-th accepted word ends the fill
-    if (done && acc && rank == take - 1) *d.s_end = tid;
-    __syncthreads();  // s_end is written; wcnt is rewritten by the next round
-    if (done) {
-      d.pos = *d.s_end + 1;
-      __syncthreads();  // (s_end is rewritten by the next fill)
-      return;
-    }
-    filled += total;
-    d.pos = kMtN;
-  }
-}
+// its owner's slab. The draw is two fills of the shared masked-rejection round (fill_masked)
+// between one draw_open and one draw_close, the gather a second resolver over gather_split.
 
 // RandomState_m.choice(s, batch - pool) then RandomState_m.choice(P * s, pool) on member m's
 // stream at its own count, as global rows owner * M + row into idx[0, batch). One workgroup.
 __device__ __forceinline__ void draw_pool_body(const SacenvReplayParams& p, const RB& r, uint32_t m, uint32_t P,
                                                int batch, int pool, int64_t* __restrict__ idx) {
-  __shared__ uint32_t blk[2][kMtN];
-  __shared__ int wcnt[kDrawThreads / kWave];
-  __shared__ int s_end;
   const int tid = threadIdx.x;
-  DrawBlock d{blk, wcnt, &s_end, 0, *r.pos(), false};
-  if (d.pos < 0) {  // a poisoned stream: draw nothing, keep the poison
+  DrawBlock d;
+  if (!draw_open(d, r)) {
     for (int i = tid; i < batch; i += kDrawThreads) idx[i] = -1;
     return;
   }
-  for (int i = tid; i < kMtN; i += kDrawThreads) blk[0][i] = r.key()[i];
-  __syncthreads();
   const int64_t M = p.mem_size, c = *r.cntr();
   const uint32_t s = (uint32_t)(c < M ? c : M);  // 1 <= s < 2^31 (the host refuses an empty ring)
   const int own = batch - pool;
@@ -194,9 +130,7 @@ __device__ __forceinline__ void draw_pool_body(const SacenvReplayParams& p, cons
       });
     }
   }
-  if (d.advanced)
-    for (int i = tid; i < kMtN; i += kDrawThreads) r.key()[i] = blk[d.cur][i];
-  if (tid == 0) *r.pos() = d.pos;
+  draw_close(d, r);
 }
 
 // grid (1, P) x 1 024 threads: one workgroup per member, each on its own key, position and count
@@ -206,48 +140,20 @@ __global__ void __launch_bounds__(kDrawThreads) k_rb_draw_pool(SacenvReplayParam
   draw_pool_body(p, member_rb(r, member_bytes, m), (uint32_t)m, gridDim.y, batch, pool, idx + m * batch);
 }
 
-// grid (ceil(batch x (D + A + 1) / 256), P): one thread per output element of member m's
-// [batch][..] outputs, in gather_body's column split (state / new_state, action, reward +
-// terminal); the row is row g % M of slab g / M, g the global index; g outside [0, P x M)
-// gives zero bits. P x M <= 2^32 and M < 2^31: 32-bit division.
+// grid (ceil(batch x (D + A + 1) / 256), P): member m's rows of the [P][batch][..] outputs; the
+// row at global index g is row g % M of slab g / M; g outside [0, P x M) gives zero bits.
+// P x M <= 2^32 and M < 2^31: 32-bit division.
 __global__ void __launch_bounds__(256) k_rb_gather_pool(SacenvReplayParams p, RB r, int64_t member_bytes, int batch,
                                                         const int64_t* __restrict__ idx, float* __restrict__ st,
                                                         float* __restrict__ ac, double* __restrict__ rw,
                                                         float* __restrict__ ns, uint8_t* __restrict__ tm) {
-  const int64_t m = blockIdx.y, rows = m * batch;
-  const int D = p.obs_dim, A = p.act_dim;
-  const int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t nd = (int64_t)batch * D, na = (int64_t)batch * A;
+  const int64_t rows = (int64_t)blockIdx.y * batch, top = (int64_t)gridDim.y * p.mem_size;
   const uint32_t M = (uint32_t)p.mem_size;
-  const int64_t top = (int64_t)gridDim.y * p.mem_size;
-  idx += rows;
-  int64_t i, k;
-  int part;
-  if (q < nd) {
-    i = q / D, k = q - i * D, part = 0;
-  } else if (q < nd + na) {
-    const int64_t qq = q - nd;
-    i = qq / A, k = qq - i * A, part = 1;
-  } else if (q < nd + na + batch) {
-    i = q - nd - na, k = 0, part = 2;
-  } else {
-    return;
-  }
-  const int64_t g = idx[i];
-  const bool in = g >= 0 && g < top;
-  const uint32_t gu = in ? (uint32_t)g : 0u, owner = gu / M;
-  const int64_t row = gu - owner * M;
-  const RB ro = member_rb(r, member_bytes, owner);
-  if (part == 0) {
-    const int64_t o = (rows + i) * D + k;
-    if (st) st[o] = in ? ro.state()[row * D + k] : 0.f;
-    if (ns) ns[o] = in ? ro.new_state()[row * D + k] : 0.f;
-  } else if (part == 1) {
-    if (ac) ac[(rows + i) * A + k] = in ? ro.action()[row * A + k] : 0.f;
-  } else {
-    if (rw) rw[rows + i] = in ? ro.reward()[row] : 0.0;
-    if (tm) tm[rows + i] = in ? ro.terminal()[row] : (uint8_t)0;
-  }
+  gather_split(p, batch, idx + rows, rows, st, ac, rw, ns, tm, [&](int64_t g) {
+    const bool in = g >= 0 && g < top;
+    const uint32_t gu = in ? (uint32_t)g : 0u, owner = gu / M;
+    return GatherRow{member_rb(r, member_bytes, owner), (int64_t)(gu - owner * M), in};
+  });
 }
 
 int rb_pop_check(const SacenvReplayParams* p, int32_t members) {

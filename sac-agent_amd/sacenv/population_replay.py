@@ -78,6 +78,18 @@ class PopulationReplay(_ReplayArena):
                          final_state=env.final_obs.view(P, n, *self.input_shape),
                          last_term=self._env_last_term(env) if reference_terminal else None)
 
+    def _idx(self, idx) -> torch.Tensor:
+        """``idx`` as a contiguous i64 ``[P, B]`` tensor on the device."""
+        idx = torch.as_tensor(idx).to(device=self.device, dtype=torch.int64).contiguous()
+        if idx.dim() != 2 or idx.shape[0] != self.P:
+            raise ValueError(f"idx must be [{self.P}, B], got {list(idx.shape)}")
+        return idx
+
+    def _check_stored(self, B: int) -> None:
+        """np.random.choice(0, B)'s refusal: nothing is drawn from an empty ring."""
+        if self.mem_cntr == 0 and B > 0:
+            raise ValueError("a must be greater than 0 unless no samples are taken")
+
     def sample(self, batch_size: int, as_bool: bool = True, pool_rows: int = 0):
         """``DeviceReplayBuffer.sample`` for every member in two launches: (states [P, B, D],
         actions [P, B, A], rewards f64 [P, B], states_, dones [P, B], idx [P, B]), member m's
@@ -91,8 +103,7 @@ class PopulationReplay(_ReplayArena):
         if pool_rows:
             return self.sample_pool(batch_size, pool_rows, as_bool)
         B = int(batch_size)
-        if self.mem_cntr == 0 and B > 0:
-            raise ValueError("a must be greater than 0 unless no samples are taken")
+        self._check_stored(B)
         st, ac, rw, ns, tm, idx = self._outputs(B, idx=True)
         _lib.check(self.lib.sacenv_replay_pop_sample(
             self._pp, self.P, self.arena.data_ptr(), B, self.mem_cntr, idx.data_ptr(), st.data_ptr(), ac.data_ptr(),
@@ -107,40 +118,32 @@ class PopulationReplay(_ReplayArena):
         B, K = int(batch_size), int(pool_rows)
         if not 0 <= K <= max(B, 0):
             raise ValueError(f"pool_rows must lie in [0, batch_size = {B}], got {K}")
-        if self.mem_cntr == 0 and B > 0:
-            raise ValueError("a must be greater than 0 unless no samples are taken")
+        self._check_stored(B)
         fn, = _lib.require(_lib.REPLAY_SHARE_EXPORTS[:1], "sacenv_population_share.h", self.lib)
         st, ac, rw, ns, tm, idx = self._outputs(B, idx=True)
         _lib.check(fn(self._pp, self.P, self.arena.data_ptr(), B, K, self.mem_cntr, idx.data_ptr(), st.data_ptr(),
                       ac.data_ptr(), rw.data_ptr(), ns.data_ptr(), tm.data_ptr(), self.stream))
         return st, ac, rw, ns, (tm.bool() if as_bool else tm), idx
 
-    def gather_pool(self, idx: torch.Tensor, as_bool: bool = True):
-        """The rows at the given global indices ``[P, B]`` (owner x mem_size + row, as a pooled
-        ``sample`` returns them), for every member, each from its owner's slab (one launch); an
-        index outside ``[0, P x mem_size)`` gives zeros."""
-        fn, = _lib.require(_lib.REPLAY_SHARE_EXPORTS[1:], "sacenv_population_share.h", self.lib)
-        idx = torch.as_tensor(idx).to(device=self.device, dtype=torch.int64).contiguous()
-        if idx.dim() != 2 or idx.shape[0] != self.P:
-            raise ValueError(f"idx must be [{self.P}, B], got {list(idx.shape)}")
+    def _gather(self, fn, idx, as_bool: bool):
+        idx = self._idx(idx)
         B = idx.shape[1]
         st, ac, rw, ns, tm, _ = self._outputs(B)
         _lib.check(fn(self._pp, self.P, self.arena.data_ptr(), B, idx.data_ptr(), st.data_ptr(), ac.data_ptr(),
                       rw.data_ptr(), ns.data_ptr(), tm.data_ptr(), self.stream))
         return st, ac, rw, ns, (tm.bool() if as_bool else tm)
 
+    def gather_pool(self, idx: torch.Tensor, as_bool: bool = True):
+        """The rows at the given global indices ``[P, B]`` (owner x mem_size + row, as a pooled
+        ``sample`` returns them), for every member, each from its owner's slab (one launch); an
+        index outside ``[0, P x mem_size)`` gives zeros."""
+        fn, = _lib.require(_lib.REPLAY_SHARE_EXPORTS[1:], "sacenv_population_share.h", self.lib)
+        return self._gather(fn, idx, as_bool)
+
     def gather(self, idx: torch.Tensor, as_bool: bool = True):
         """The rows at the given ring indices ``[P, B]``, for every member (one launch); an
         index outside the ring gives zeros."""
-        idx = torch.as_tensor(idx).to(device=self.device, dtype=torch.int64).contiguous()
-        if idx.dim() != 2 or idx.shape[0] != self.P:
-            raise ValueError(f"idx must be [{self.P}, B], got {list(idx.shape)}")
-        B = idx.shape[1]
-        st, ac, rw, ns, tm, _ = self._outputs(B)
-        _lib.check(self.lib.sacenv_replay_pop_gather(
-            self._pp, self.P, self.arena.data_ptr(), B, idx.data_ptr(), st.data_ptr(), ac.data_ptr(), rw.data_ptr(),
-            ns.data_ptr(), tm.data_ptr(), self.stream))
-        return st, ac, rw, ns, (tm.bool() if as_bool else tm)
+        return self._gather(self.lib.sacenv_replay_pop_gather, idx, as_bool)
 
     def export_member(self, m: int) -> DeviceReplayBuffer:
         """A stand-alone ``DeviceReplayBuffer`` with a copy of member m's arena and count."""

@@ -82,8 +82,7 @@ class PrioritizedPopulationReplay(PopulationReplay):
         if pool_rows:
             raise ValueError("a prioritized sample draws from the member's own ring: pool_rows must be 0")
         B = int(batch_size)
-        if self.mem_cntr == 0 and B > 0:
-            raise ValueError("a must be greater than 0 unless no samples are taken")
+        self._check_stored(B)
         st, ac, rw, ns, tm, idx = self._outputs(B, idx=True)
         leaf = torch.empty(self.P, B, dtype=torch.int32, device=self.device)
         w = torch.empty(self.P, B, dtype=torch.float32, device=self.device)
@@ -100,12 +99,6 @@ class PrioritizedPopulationReplay(PopulationReplay):
         raise ValueError("a prioritized replay does not pool: pool_rows must be 0")
 
     # ---- priorities
-
-    def _idx(self, idx):
-        idx = torch.as_tensor(idx).to(device=self.device, dtype=torch.int64).contiguous()
-        if idx.dim() != 2 or idx.shape[0] != self.P:
-            raise ValueError(f"idx must be [{self.P}, B], got {list(idx.shape)}")
-        return idx
 
     def set_priorities(self, idx, leaf) -> None:
         """Explicit priorities: u32 fixed point (65 536 = 1.0) ``[P, B]`` for the ring rows ``idx``

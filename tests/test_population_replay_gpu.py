@@ -218,6 +218,37 @@ def test_sample_matches_stand_alone_buffers_and_numpy(gpu, built_lib, M, held, b
     assert got[4].dtype == torch.bool and torch.equal(got[4][0], refs[0].sample(batch)[4])
 
 
+def test_sample_that_ends_on_the_last_word_of_a_block(gpu, built_lib):
+    """``RandomState(105).choice(100, 1000)`` accepts word 623 of a block as its last: the
+    position written back is 624, and the next sample has to twist before its first word."""
+    from sacenv.population_replay import PopulationReplay
+    from sacenv.replay import DeviceReplayBuffer
+    P, M, held, batch = 3, 100, 128, 1000
+    D, A = SHAPES[M]
+    seeds = [7, 105, 20]
+    pop = PopulationReplay(P, M, (D,), A, device=gpu, seeds=seeds)
+    refs = [DeviceReplayBuffer(M, (D,), A, device=gpu, seed=s) for s in seeds]
+    big = _guard(pop)
+    for k in range(2):
+        _store_both(pop, refs, _rows(gpu, P, 64, M, 9500 + k), extras=False)
+    probe = np.random.RandomState(105)
+    probe.choice(M, batch)
+    assert probe.get_state()[2] == 624
+    rng = [np.random.RandomState(s) for s in seeds]
+    for call in range(3):
+        got = pop.sample(batch, as_bool=False)
+        for m, ref in enumerate(refs):
+            want = ref.sample(batch, as_bool=False)
+            for x, y in zip(got, want):
+                assert torch.equal(x[m], y), f"member {m}, call {call}"
+            assert np.array_equal(got[5][m].cpu().numpy(), rng[m].choice(M, batch)), \
+                f"member {m}, call {call}: not numpy's draws"
+        _same_arenas(pop, refs, f"after sample {call}")
+        if call == 0:
+            assert pop.arena[1, pop.layout.mt_pos: pop.layout.mt_pos + 4].view(torch.int32).item() == 624
+    assert _guard_ok(big)
+
+
 def test_one_member_is_one_buffer(gpu, built_lib):
     """P = 1 runs the one-buffer kernels (the branch in sacenv_replay_pop.hip): both count
     forms of the store, the sample and the gather."""

@@ -36,16 +36,16 @@ def _seeds(P):
     return [7 + 13 * m for m in range(P)]
 
 
-def _new(gpu, P, M):
+def _new(gpu, P, M, seeds=None):
     from sacenv.population_replay import PopulationReplay
-    return PopulationReplay(P, M, (D,), A, device=gpu, seeds=_seeds(P))
+    return PopulationReplay(P, M, (D,), A, device=gpu, seeds=seeds or _seeds(P))
 
 
 @functools.lru_cache(maxsize=None)
-def _filled(gpu, P, M, count):
+def _filled(gpu, P, M, count, seeds=None):
     """(replay, its arena after the stores, the members' rings as numpy [P, M, ...] in the
     outputs' order): built once per shape; a test copies the snapshot back before it samples."""
-    pop = _new(gpu, P, M)
+    pop = _new(gpu, P, M, seeds)
     g = torch.Generator().manual_seed(1000 * P + M + count)
     left = count
     while left:
@@ -98,6 +98,29 @@ def test_indices_rows_and_stream_match_numpy(gpu, built_lib, P, M, count, B, K):
         got = pop.sample(B, as_bool=False, pool_rows=K)
         assert np.array_equal(got[5].cpu().numpy(), share_oracle.draw(rngs, P, M, count, B, K))
         assert pop.sample(B, pool_rows=K)[4].dtype == torch.bool
+
+
+def test_own_fill_that_ends_on_the_last_word_of_a_block(gpu, built_lib):
+    """Member 1 (seed 582, found by a search on the CPU): the own fill of its second call,
+    ``choice(100, 192)``, accepts word 623 of a block as its last, so the pool fill that follows on
+    the same block pair starts at position 624 and has to twist first."""
+    P, M, count, B, K = 3, 100, 128, 256, 64
+    seeds = (7, 582, 20)
+    pop, snap, rings = _filled(gpu, P, M, count, seeds)
+    pop.arena.copy_(snap)
+    s = min(count, M)
+    probe = np.random.RandomState(seeds[1])
+    probe.choice(s, B - K), probe.choice(P * s, K), probe.choice(s, B - K)
+    assert probe.get_state()[2] == 624
+    rngs = [np.random.RandomState(x) for x in seeds]
+    for call in range(3):
+        got = pop.sample_pool(B, K, as_bool=False)
+        want = share_oracle.draw(rngs, P, M, count, B, K)
+        assert np.array_equal(got[5].cpu().numpy(), want), f"call {call}: not numpy's draws"
+        _same_bytes(got[:5], share_oracle.gather(rings, want, M), f"call {call}")
+    nxt = pop.sample(64, as_bool=False)[5].cpu().numpy()
+    for m in range(P):
+        assert np.array_equal(nxt[m], rngs[m].choice(s, 64)), f"member {m}: the stream after the pooled draws"
 
 
 def test_every_output_may_be_null(gpu, built_lib):
