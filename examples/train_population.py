@@ -13,7 +13,8 @@ as OS processes, three at a time; here they are the members of one ``NativeSACPo
 * an ``EpisodeLog`` on the env; an episode of env e belongs to member e // N.
 
     python examples/train_population.py --members 4 --envs-per-member 1024 --iters 200 [--seed 0]
-        [--replay population|members] [--share-replay K] [--prioritized [ALPHA]] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
+        [--replay population|members] [--share-replay K] [--prioritized [ALPHA] [--importance-weights [BETA]
+        [--beta-final B1 --beta-anneal N]]] [--noise torch|counter] [--noise-seed 0] [--keep-best DIR]
         [--select-every K [--quantile Q] [--min-episodes E] [--select-seed 0]] [--keep-traces DIR
         [--render DIR [--render-every K]]]
 
@@ -31,9 +32,19 @@ surprising transitions more often: the replay is a ``PrioritizedPopulationReplay
 (include/sacenv_prioritized_replay.h), every member samples its own rows in proportion to (|TD error|
 + eps)^ALPHA (default 0.6) from a sum tree on the device, new rows enter at the largest priority so
 far, and after each learn the batch's rows take the priorities of the TD errors the learn kernels
-left behind. The importance weights are computed (``replay.last_weights``) but NOT applied in the
-learn; whether prioritizing speeds learning up has not been measured. The JSON line gains
-``prioritized`` (alpha, beta, eps and each member's priority total). Without the flag nothing changes.
+left behind. The importance weights (``replay.last_weights``) are applied in the learn with
+``--importance-weights`` (below) and not without it; whether prioritizing speeds learning up has not
+been measured, with or without them. The JSON line gains ``prioritized`` (alpha, beta, eps and each
+member's priority total). Without the flag nothing changes.
+
+``--importance-weights [BETA]`` (with ``--prioritized``) applies the sample's importance weights,
+(min leaf / leaf)^BETA (default 0.4), to the critics' TD loss (``NativeSACPopulation(...,
+importance_weights=True)``, include/sacenv_weighted_learn.h): each batch row's critic gradient and
+loss term is scaled by its weight, while the priorities still follow the raw TD errors.
+``--beta-final B1 --beta-anneal N`` let the exponent run from BETA to B1 over the first N samples,
+computed on the device from the sample's number. ``prioritized`` in the JSON line gains
+``importance_weights``, ``beta_final``, ``beta_anneal`` and ``beta_now`` (the last sample's exponent).
+Without the flag nothing changes.
 
 ``--noise counter`` gives member m the noise seed ``--noise-seed`` + m (``sacenv.PolicyNoise``): the
 act draw and both learn draws of an iteration come from one launch for all members, and member m's
@@ -104,6 +115,13 @@ def main(argv=None):
     ap.add_argument("--prioritized", type=float, nargs="?", const=0.6, default=None, metavar="ALPHA",
                     help="sample every member's rows in proportion to (|TD error| + eps)^ALPHA (needs --replay "
                          "population; excludes --share-replay)")
+    ap.add_argument("--importance-weights", type=float, nargs="?", const=0.4, default=None, metavar="BETA",
+                    help="apply the sample's importance weights (min leaf / leaf)^BETA in the critic loss (needs "
+                         "--prioritized; bare: 0.4)")
+    ap.add_argument("--beta-final", type=float, default=None, metavar="B1",
+                    help="anneal the weights' exponent from BETA to B1 (needs --importance-weights and --beta-anneal)")
+    ap.add_argument("--beta-anneal", type=int, default=None, metavar="N",
+                    help="the samples the exponent takes from BETA to B1")
     ap.add_argument("--noise", choices=("torch", "counter"), default="torch",
                     help="policy noise from torch's stream, or counter-based with one seed per member")
     ap.add_argument("--noise-seed", type=int, default=0, help="member m's noise seed is this + m")
@@ -141,6 +159,18 @@ def main(argv=None):
             ap.error("--prioritized samples a member's own rows: it excludes --share-replay")
         if not 0 <= args.prioritized < float("inf"):
             ap.error("--prioritized takes a finite ALPHA >= 0")
+    if args.importance_weights is not None:
+        if args.prioritized is None:
+            ap.error("--importance-weights applies the weights of a --prioritized sample")
+        if not 0 <= args.importance_weights < float("inf"):
+            ap.error("--importance-weights takes a finite BETA >= 0")
+    if args.beta_final is not None or args.beta_anneal is not None:
+        if args.importance_weights is None:
+            ap.error("--beta-final and --beta-anneal anneal the exponent of --importance-weights")
+        if args.beta_final is None or args.beta_anneal is None:
+            ap.error("--beta-final and --beta-anneal go together")
+        if not 0 <= args.beta_final < float("inf") or args.beta_anneal < 1:
+            ap.error("--beta-final takes a finite B1 >= 0, --beta-anneal N >= 1")
     P, N = args.members, args.envs_per_member
     if N < 64 or N % 64:
         raise SystemExit("--envs-per-member must be a multiple of 64 (the act kernel's row block)")
@@ -151,14 +181,20 @@ def main(argv=None):
     configs = sample_hpsets(P, args.seed, base=AgentConfig(batch_size=args.batch))
     pooled = args.replay == "population"
     replay = None
+    weighted = args.importance_weights is not None
     if args.prioritized is not None:
         from sacenv import PrioritizedPopulationReplay
+        extra = {}
+        if weighted:
+            extra.update(beta=args.importance_weights)
+            if args.beta_final is not None:
+                extra.update(beta_final=args.beta_final, beta_anneal=args.beta_anneal)
         replay = PrioritizedPopulationReplay(P, configs[0].max_size, (11,), 1, device=dev, seeds=list(range(P)),
-                                             alpha=args.prioritized)
+                                             alpha=args.prioritized, **extra)
     elif pooled:  # the members' buffers in one arena, with the seeds the per-member buffers get
         replay = PopulationReplay(P, configs[0].max_size, (11,), 1, device=dev, seeds=list(range(P)))
     pop = NativeSACPopulation(dev, configs, init_seeds=list(range(P)), buffer_seeds=list(range(P)), replay=replay,
-                              pool_rows=share,
+                              pool_rows=share, **({"importance_weights": True} if weighted else {}),
                               noise_seeds=[args.noise_seed + m for m in range(P)] if args.noise == "counter" else None)
     for m, mem in enumerate(pop.members):
         print(f"member {m}: " + json.dumps(mem.hpset()))
@@ -278,6 +314,10 @@ def main(argv=None):
     if args.prioritized is not None:
         out.update(prioritized={"alpha": replay.alpha, "beta": replay.beta, "eps": replay.eps,
                                 "totals": [replay.total(m) for m in range(P)]})
+        if weighted:
+            out["prioritized"].update(importance_weights=True, beta_final=replay.beta_final,
+                                      beta_anneal=replay.beta_anneal,
+                                      beta_now=replay.beta_at(max(replay.sample_calls - 1, 0)))
     if board is not None:
         out.update(device_table=device_table, kept=kept, best_member=board.best_member())
     if selection is not None:

@@ -26,11 +26,13 @@
 //
 // The prioritized sample (include/sacenv_prioritized_replay.h) has its entry points
 // at the end; its device code is sacenv_replay_prio.h, and its gather is k_rb_gather_pop above.
+// The annealed sample of include/sacenv_weighted_learn.h is the same launches with one more argument.
 #include "sacenv_replay_core.h"
 
 #include "sacenv_population_replay.h"
 #include "sacenv_population_share.h"
 #include "sacenv_replay_prio.h"
+#include "sacenv_weighted_learn.h"   // (the annealed prioritized sample, the last entry point here)
 
 namespace {
 
@@ -371,12 +373,13 @@ __global__ void __launch_bounds__(kPrioThreads) k_prio_draw(PT t, int batch, int
   prio_draw_body(t, prio_slab(t, m), (uint32_t)m, batch, call, seeds.v[m], idx + m * batch, leaf_out + m * batch);
 }
 
-// grid (1, P)
+// grid (1, P); kAnneal: the exponent by the sample's number (include/sacenv_weighted_learn.h)
+template <bool kAnneal>
 __global__ void __launch_bounds__(kPrioMemberThreads) k_prio_finish(PT t, int batch, const uint32_t* __restrict__ leaf_out,
-                                                              float* __restrict__ weights, double beta, int advance) {
+                                                              float* __restrict__ weights, PrioBeta b, int advance) {
   const int64_t m = blockIdx.y;
-  prio_finish_body(prio_slab(t, m), batch, leaf_out + m * batch, weights != nullptr ? weights + m * batch : nullptr,
-                   beta, advance != 0);
+  prio_finish_body<kAnneal>(prio_slab(t, m), batch, leaf_out + m * batch,
+                            weights != nullptr ? weights + m * batch : nullptr, b, advance != 0);
 }
 
 bool finite_nonneg(double x) { return x >= 0.0 && x <= 1.7976931348623157e308; }  // (false for NaN)
@@ -477,14 +480,12 @@ extern "C" int sacenv_replay_prio_update_td(const SacenvReplayParams* p, int32_t
                           stream);
 }
 
-extern "C" int sacenv_replay_prio_sample(const SacenvReplayParams* p, int32_t members, void* arena, void* state,
-                                         int32_t batch, int64_t call, const uint64_t* seeds, int64_t* idx,
-                                         uint32_t* leaf_out, float* weights, double beta, float* st, float* action,
-                                         double* reward, float* new_state, uint8_t* terminal, void* stream) {
-  int rc = rb_pop_check(p, members);
-  if (rc) return rc;
-  if (batch < 0) return SACENV_E_SIZE;
-  if (call < -1 || !finite_nonneg(beta)) return SACENV_E_RANGE;
+namespace {
+
+// the launches of both samples, after their checks: b.anneal == 0 is the plain one
+int prio_sample(const SacenvReplayParams* p, int32_t members, void* arena, void* state, int32_t batch, int64_t call,
+                const uint64_t* seeds, int64_t* idx, uint32_t* leaf_out, float* weights, const PrioBeta& b, float* st,
+                float* action, double* reward, float* new_state, uint8_t* terminal, void* stream) {
   if (batch == 0) return SACENV_OK;
   if (arena == nullptr || state == nullptr || seeds == nullptr || idx == nullptr || leaf_out == nullptr)
     return SACENV_E_NULL;
@@ -495,9 +496,44 @@ extern "C" int sacenv_replay_prio_sample(const SacenvReplayParams* p, int32_t me
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_prio_draw, dim3((unsigned)(((int64_t)batch + 3) / 4), members), dim3(kPrioThreads), 0, s, t,
                      (int)batch, call, sd, idx, leaf_out);
-  if (weights != nullptr || call < 0)
-    hipLaunchKernelGGL(k_prio_finish, dim3(1, members), dim3(kPrioMemberThreads), 0, s, t, (int)batch, leaf_out, weights,
-                       beta, call < 0 ? 1 : 0);
-  if ((rc = status())) return rc;
+  if (weights != nullptr || call < 0) {
+    if (b.anneal > 0)
+      hipLaunchKernelGGL(k_prio_finish<true>, dim3(1, members), dim3(kPrioMemberThreads), 0, s, t, (int)batch,
+                         leaf_out, weights, b, call < 0 ? 1 : 0);
+    else
+      hipLaunchKernelGGL(k_prio_finish<false>, dim3(1, members), dim3(kPrioMemberThreads), 0, s, t, (int)batch,
+                         leaf_out, weights, b, call < 0 ? 1 : 0);
+  }
+  const int rc = status();
+  if (rc) return rc;
   return sacenv_replay_pop_gather(p, members, arena, batch, idx, st, action, reward, new_state, terminal, stream);
+}
+
+}  // namespace
+
+extern "C" int sacenv_replay_prio_sample(const SacenvReplayParams* p, int32_t members, void* arena, void* state,
+                                         int32_t batch, int64_t call, const uint64_t* seeds, int64_t* idx,
+                                         uint32_t* leaf_out, float* weights, double beta, float* st, float* action,
+                                         double* reward, float* new_state, uint8_t* terminal, void* stream) {
+  const int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (batch < 0) return SACENV_E_SIZE;
+  if (call < -1 || !finite_nonneg(beta)) return SACENV_E_RANGE;
+  return prio_sample(p, members, arena, state, batch, call, seeds, idx, leaf_out, weights, PrioBeta{beta, beta, 0, call},
+                     st, action, reward, new_state, terminal, stream);
+}
+
+// ---- include/sacenv_weighted_learn.h: the sample with its weights' exponent annealed
+extern "C" int sacenv_replay_prio_sample_annealed(const SacenvReplayParams* p, int32_t members, void* arena,
+                                                  void* state, int32_t batch, int64_t call, const uint64_t* seeds,
+                                                  int64_t* idx, uint32_t* leaf_out, float* weights, double beta0,
+                                                  double beta1, int64_t anneal_calls, float* st, float* action,
+                                                  double* reward, float* new_state, uint8_t* terminal,
+                                                  void* stream) {
+  const int rc = rb_pop_check(p, members);
+  if (rc) return rc;
+  if (batch < 0) return SACENV_E_SIZE;
+  if (call < -1 || !finite_nonneg(beta0) || !finite_nonneg(beta1) || anneal_calls < 1) return SACENV_E_RANGE;
+  return prio_sample(p, members, arena, state, batch, call, seeds, idx, leaf_out, weights,
+                     PrioBeta{beta0, beta1, anneal_calls, call}, st, action, reward, new_state, terminal, stream);
 }

@@ -320,10 +320,31 @@ __device__ __forceinline__ void prio_draw_body(const PT& t, char* slab, uint32_t
 }
 
 // ---- after the draw: grid (1, P) x 1 024 (a pow per thread at batch 1 024). weights = (min leaf / leaf)^beta, and the count's advance
+// kAnneal (include/sacenv_weighted_learn.h): beta runs from b.beta to b.beta1 over b.anneal samples,
+// by the sample's number -- b.call, or the slab's count from BEFORE this sample's advance, which
+// thread 0 reads once and hands to the others through LDS before it advances
+struct PrioBeta {
+  double beta, beta1;
+  int64_t anneal, call;
+};
+
+template <bool kAnneal>
 __device__ __forceinline__ void prio_finish_body(char* slab, int batch, const uint32_t* __restrict__ leaf_out,
-                                                 float* __restrict__ weights, double beta, bool advance) {
+                                                 float* __restrict__ weights, const PrioBeta& b, bool advance) {
   __shared__ uint32_t s_min[kPrioMemberThreads / kWave];
+  __shared__ int64_t s_calls;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+  double beta = b.beta;
+  if (kAnneal) {
+    int64_t k = b.call;
+    if (k < 0) {
+      if (tid == 0) s_calls = prio_header(slab)->calls;
+      __syncthreads();
+      k = s_calls;
+    }
+    k = k < b.anneal ? k : b.anneal;
+    beta = b.beta + (b.beta1 - b.beta) * ((double)k / (double)b.anneal);
+  }
   if (advance && tid == 0) prio_header(slab)->calls += 1;
   if (weights == nullptr) return;
   uint32_t mn = 0xFFFFFFFFu;

@@ -40,6 +40,8 @@
 // one-agent kernels and the entry points of include/sacenv.h.
 #include "sacenv_sac_core.h"
 
+#include "sacenv_weighted_learn.h"   // (sacenv_sac_learn_weighted: the learn with a weight per row)
+
 namespace {
 
 // one or two workgroups per CU: registers for kPrefetch k-blocks of weights in flight
@@ -167,10 +169,11 @@ extern "C" int sacenv_sac_act_handoff(const SacenvSacParams* p, const float* wei
                  stream);
 }
 
-extern "C" int sacenv_sac_learn(const SacenvSacParams* p, float* weights, void* scratch, const float* state,
-                                const float* action, const double* reward, const float* new_state,
-                                const uint8_t* done, const float* eps1, const float* eps2, int32_t adam_step,
-                                float* losses, void* stream) {
+// include/sacenv_weighted_learn.h: row_weights [batch] or null (sacenv_sac_learn: null)
+extern "C" int sacenv_sac_learn_weighted(const SacenvSacParams* p, float* weights, void* scratch, const float* state,
+                                         const float* action, const double* reward, const float* new_state,
+                                         const uint8_t* done, const float* eps1, const float* eps2,
+                                         int32_t adam_step, float* losses, const float* row_weights, void* stream) {
   const int rc = check(p);
   if (rc != SACENV_OK) return rc;
   if (weights == nullptr || scratch == nullptr || state == nullptr || action == nullptr || reward == nullptr ||
@@ -187,6 +190,7 @@ extern "C" int sacenv_sac_learn(const SacenvSacParams* p, float* weights, void* 
   a.eps1 = eps1;
   a.eps2 = eps2;
   a.losses = losses;
+  a.isw = row_weights;
   const double bc1 = set_learn_common(a, p, scratch, adam_step);
   set_member(a, member_scalars(p->lr_actor, p->lr_critic, p->gamma, p->tau, p->reward_scale, bc1));
   const int nrb = p->batch / kRows;
@@ -196,4 +200,12 @@ extern "C" int sacenv_sac_learn(const SacenvSacParams* p, float* weights, void* 
   hipLaunchKernelGGL(k_sac_rows, dim3(4 * nrb), dim3(kThreads), 0, s, a, 2);
   hipLaunchKernelGGL(k_sac_update, dim3(kUpdateBlocks), dim3(kThreads), 0, s, a);
   return (int)hipGetLastError();
+}
+
+extern "C" int sacenv_sac_learn(const SacenvSacParams* p, float* weights, void* scratch, const float* state,
+                                const float* action, const double* reward, const float* new_state,
+                                const uint8_t* done, const float* eps1, const float* eps2, int32_t adam_step,
+                                float* losses, void* stream) {
+  return sacenv_sac_learn_weighted(p, weights, scratch, state, action, reward, new_state, done, eps1, eps2, adam_step,
+                                   losses, nullptr, stream);
 }

@@ -113,6 +113,7 @@ struct SacArgs {
   // Adam (torch.optim.Adam foreach form), scalars as torch casts them
   float lerp_w, b2, omb2, bc2s, eps, nstep_actor, nstep_critic;
   float tau, omtau;
+  const float* isw;    // importance weights [B] of the critic loss (sacenv_weighted_learn.h), or null
 };
 
 __device__ __forceinline__ float* rowf(const SacArgs& a, int f) { return a.rows + (int64_t)f * a.B; }
@@ -540,7 +541,16 @@ __device__ void role_critic_loss(const SacArgs& a, RowLds& l, int tid, int row0,
     const float g = d * a.inv_b;  // mse backward: (2 / B) (q - q_hat) * 0.5
     l.g0[tid] = g;
     rowf(a, c == 1 ? F_GC1 : F_GC2)[r] = g;
-    rowf(a, c == 1 ? F_LC1 : F_LC2)[r] = d * d;
+    rowf(a, c == 1 ? F_LC1 : F_LC2)[r] = d * d;  // raw, weighted or not: the priority update reads it
+    // The row's importance weight (sacenv_weighted_learn.h) replaces g in a block of its own, after
+    // the unweighted stores. As `if (isw) g = (w d) / B` in front of them, the population's row
+    // kernel, whose member arguments fill the scalar registers, spilled twice as many of them in
+    // every role, and an unweighted learn() took 1 % longer.
+    if (a.isw != nullptr) {
+      const float gw = (a.isw[r] * d) * a.inv_b;
+      l.g0[tid] = gw;
+      rowf(a, c == 1 ? F_GC1 : F_GC2)[r] = gw;
+    }
   }
   lds_sync();
   head_backward(a.P + a.net[c], a.off[kCriticShape], a.P + a.w2tf[c], pre, l, tid, na.dz2t, na.dz1t, a.B, row0,
@@ -832,7 +842,10 @@ __device__ void reduce_losses(const SacArgs& a, int tid, float* xs) {
   for (int q = 0; q < 4; ++q) {  // F_LV, F_LA, F_LC1, F_LC2 are consecutive
     const float* v = rowf(a, F_LV + q);
     float s = 0.f;
-    for (int r = tid; r < a.B; r += kThreads) s += v[r];
+    if (q >= 2 && a.isw != nullptr)  // the critics' rows, by their importance weights
+      for (int r = tid; r < a.B; r += kThreads) s += a.isw[r] * v[r];
+    else
+      for (int r = tid; r < a.B; r += kThreads) s += v[r];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
     if ((tid & 63) == 0) xs[4 * q + (tid >> 6)] = s;

@@ -25,6 +25,7 @@
 #pragma clang attribute pop
 
 #include "sacenv_prioritized_replay.h"   // (its one accessor of the learn scratch lives here, at the end)
+#include "sacenv_weighted_learn.h"       // (sacenv_sac_pop_learn_weighted: the learn with a weight per row)
 
 namespace {
 
@@ -66,6 +67,7 @@ __device__ __forceinline__ SacArgs member_args(const SacArgs& a, const PopArgs& 
     am.done = a.done + rows;
     am.eps1 = a.eps1 + rows;
     am.eps2 = a.eps2 + rows;
+    if (a.isw != nullptr) am.isw = a.isw + rows;
   }
   const PopMember h = q.hp[m];
   am.gamma = h.gamma;
@@ -206,11 +208,13 @@ extern "C" int sacenv_sac_pop_act(const SacenvSacParams* p, int32_t members, con
   return (int)hipGetLastError();
 }
 
-extern "C" int sacenv_sac_pop_learn(const SacenvSacParams* p, int32_t members, const SacenvSacMember* hp,
-                                    float* weights, void* scratch, const float* state, const float* action,
-                                    const double* reward, const float* new_state, const uint8_t* done,
-                                    const float* eps1, const float* eps2, int32_t adam_step, float* losses,
-                                    void* stream) {
+// include/sacenv_weighted_learn.h: row_weights [members][batch] or null (sacenv_sac_pop_learn: null)
+extern "C" int sacenv_sac_pop_learn_weighted(const SacenvSacParams* p, int32_t members, const SacenvSacMember* hp,
+                                             float* weights, void* scratch, const float* state,
+                                             const float* action, const double* reward, const float* new_state,
+                                             const uint8_t* done, const float* eps1, const float* eps2,
+                                             int32_t adam_step, float* losses, const float* row_weights,
+                                             void* stream) {
   const int rc = pop_check(p, members, false);
   if (rc != SACENV_OK) return rc;
   if (hp == nullptr || weights == nullptr || scratch == nullptr || state == nullptr || action == nullptr ||
@@ -229,8 +233,8 @@ extern "C" int sacenv_sac_pop_learn(const SacenvSacParams* p, int32_t members, c
     one.gamma = hp[0].gamma;
     one.tau = hp[0].tau;
     one.reward_scale = hp[0].reward_scale;
-    return sacenv_sac_learn(&one, weights, scratch, state, action, reward, new_state, done, eps1, eps2, adam_step,
-                            losses, stream);
+    return sacenv_sac_learn_weighted(&one, weights, scratch, state, action, reward, new_state, done, eps1, eps2,
+                                     adam_step, losses, row_weights, stream);
   }
   SacenvSacPopLayout L;
   make_pop_layout(p, members, &L);
@@ -243,6 +247,7 @@ extern "C" int sacenv_sac_pop_learn(const SacenvSacParams* p, int32_t members, c
   a.eps1 = eps1;
   a.eps2 = eps2;
   a.losses = losses;
+  a.isw = row_weights;
   const double bc1 = set_learn_common(a, p, scratch, adam_step);
   PopArgs q{};
   q.w_stride = L.member_floats;
@@ -257,6 +262,15 @@ extern "C" int sacenv_sac_pop_learn(const SacenvSacParams* p, int32_t members, c
   hipLaunchKernelGGL(k_sac_rows_pop, dim3(4 * nrb, members), dim3(kThreads), 0, s, a, q, 2);
   hipLaunchKernelGGL(k_sac_update_pop, dim3(kUpdateBlocksPop, members), dim3(kThreads), 0, s, a, q);
   return (int)hipGetLastError();
+}
+
+extern "C" int sacenv_sac_pop_learn(const SacenvSacParams* p, int32_t members, const SacenvSacMember* hp,
+                                    float* weights, void* scratch, const float* state, const float* action,
+                                    const double* reward, const float* new_state, const uint8_t* done,
+                                    const float* eps1, const float* eps2, int32_t adam_step, float* losses,
+                                    void* stream) {
+  return sacenv_sac_pop_learn_weighted(p, members, hp, weights, scratch, state, action, reward, new_state, done, eps1,
+                                       eps2, adam_step, losses, nullptr, stream);
 }
 
 // ---- include/sacenv_prioritized_replay.h: where role_critic_loss leaves (q - q_hat)^2 per batch

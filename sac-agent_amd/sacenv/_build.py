@@ -26,7 +26,8 @@ HEADERS = ("mt19937.h", "sacenv_replay_core.h", "sacenv_sac_core.h", "sacenv_phi
            "sacenv_traces_frames.h", "sacenv_replay_prio.h")
 PUBLIC_HEADERS = ("sacenv.h", "sacenv_episodes.h", "sacenv_population.h", "sacenv_population_replay.h",
                   "sacenv_noise.h", "sacenv_scoreboard.h", "sacenv_selection.h", "sacenv_traces.h",
-                  "sacenv_frames.h", "sacenv_population_share.h", "sacenv_prioritized_replay.h")
+                  "sacenv_frames.h", "sacenv_population_share.h", "sacenv_prioritized_replay.h",
+                  "sacenv_weighted_learn.h")
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fPIC", "-shared", "-Wall")
 

@@ -341,6 +341,31 @@ class ReplayPrioLayout(C.Structure):
                 ("count", _i64 * REPLAY_PRIO_MAX_LEVELS), ("offset", _i64 * REPLAY_PRIO_MAX_LEVELS)]
 
 
+# include/sacenv_weighted_learn.h (SACENV_WEIGHTED_LEARN_VERSION 1): the learn with an importance
+# weight per batch row, and the prioritized sample with its weights' exponent annealed; beside the
+# ABI of sacenv.h, looked up only where the feature is used (weighted_learn_fn)
+WEIGHTED_LEARN_VERSION = 1
+WEIGHTED_LEARN_HEADER = "sacenv_weighted_learn.h"
+WEIGHTED_LEARN_EXPORTS = ("sacenv_sac_learn_weighted", "sacenv_sac_pop_learn_weighted",
+                          "sacenv_replay_prio_sample_annealed")
+
+
+def weighted_learn_fn(name: str, lib=None):
+    """Entry point ``name`` of sacenv_weighted_learn.h with its argument types set; a library built
+    before the header raises ``SacenvError``."""
+    QP, RP = C.POINTER(SacParams), C.POINTER(ReplayParams)
+    args = {
+        "sacenv_sac_learn_weighted": [QP, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p],
+        "sacenv_sac_pop_learn_weighted": [QP, _i32, C.POINTER(SacMember), _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32,
+                                          _p, _p, _p],
+        "sacenv_replay_prio_sample_annealed": [RP, _i32, _p, _p, _i32, _i64, C.POINTER(C.c_uint64), _p, _p, _p, _d,
+                                               _d, _i64, _p, _p, _p, _p, _p, _p],
+    }[name]
+    fn, = require((name,), WEIGHTED_LEARN_HEADER, lib)
+    fn.restype, fn.argtypes = C.c_int, args
+    return fn
+
+
 class Frames(C.Structure):
     """SacenvFrames (sacenv_frames.h)."""
     _fields_ = [("width", _i32), ("height", _i32), ("strip", _i32), ("members", _i32), ("max_steps", _i32),

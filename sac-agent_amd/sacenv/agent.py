@@ -161,10 +161,13 @@ class VecSAC:
         for tp, p in zip(self.target_value.parameters(), self.value.parameters()):
             tp.copy_(tau * p.clone() + (1 - tau) * tp.clone())
 
-    def learn(self, batch=None, noise=None):
+    def learn(self, batch=None, noise=None, weights=None):
         """continuous_agent.py:96-154. ``batch`` = (state, action, reward, new_state, done)
         (else sampled from the device buffer, buffer.py:24-35); ``noise`` = (eps of the
-        sample() draw, eps of the rsample() draw), each [B, n_actions].
+        sample() draw, eps of the rsample() draw), each [B, n_actions]. ``weights`` [B]: a weight
+        per row on the critics' TD loss, 0.5 * mean(w * (q - q_hat)^2) (the importance weights of a
+        prioritized sample; ``NativeSAC.learn(weights=)`` is this on the device); ``None``: the
+        reference's loss.
         Returns (value_loss, actor_loss, critic_1_loss, critic_2_loss) or None."""
         if batch is None:
             if self.memory is None or self.memory.mem_cntr < self.cfg.batch_size:
@@ -205,8 +208,13 @@ class VecSAC:
         self.opt_c1.zero_grad()
         self.opt_c2.zero_grad()
         q_hat = self.cfg.reward_scale * reward + self.cfg.gamma * value_.detach()
-        critic_1_loss = 0.5 * F.mse_loss(self.critic_1(state, action).view(-1), q_hat)
-        critic_2_loss = 0.5 * F.mse_loss(self.critic_2(state, action).view(-1), q_hat)
+        if weights is None:
+            critic_1_loss = 0.5 * F.mse_loss(self.critic_1(state, action).view(-1), q_hat)
+            critic_2_loss = 0.5 * F.mse_loss(self.critic_2(state, action).view(-1), q_hat)
+        else:
+            w = torch.as_tensor(weights, device=dev).to(torch.float32).view(-1)
+            critic_1_loss = 0.5 * torch.mean(w * (self.critic_1(state, action).view(-1) - q_hat) ** 2)
+            critic_2_loss = 0.5 * torch.mean(w * (self.critic_2(state, action).view(-1) - q_hat) ** 2)
         (critic_1_loss + critic_2_loss).backward()
         self.opt_c1.step()
         self.opt_c2.step()

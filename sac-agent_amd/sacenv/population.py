@@ -110,11 +110,23 @@ class NativeSACPopulation(_SacCore):
     members' rings (include/sacenv_population_share.h); a member still learns once its own ring
     holds B rows, and with K > 0 its weights depend on the other members' rows. With a
     ``PrioritizedPopulationReplay`` as ``replay=`` (sacenv/prioritized.py) a ``learn()`` that sampled
-    the replay itself hands the batch's TD errors back to it afterwards."""
+    the replay itself hands the batch's TD errors back to it afterwards; with
+    ``importance_weights=True`` such a ``learn()`` also passes the sample's importance weights
+    (``memory.last_weights``) as its ``weights=`` (include/sacenv_weighted_learn.h)."""
+
+    _learn_weighted_name = "sacenv_sac_pop_learn_weighted"
 
     def __init__(self, device, configs, *, obs_dim: int = 11, max_action: float = 1.0, init_seeds=None,
                  buffer_seeds=None, with_memory: bool = True, adam_eps: float = 1e-8, replay=None,
-                 noise_seeds=None, pool_rows: int = 0, _build: bool = True):
+                 noise_seeds=None, pool_rows: int = 0, importance_weights: bool = False, _build: bool = True):
+        # the sample's importance weights in the critic loss: only a prioritized replay has them
+        # (checked before a device is looked for)
+        self.importance_weights = bool(importance_weights)
+        if self.importance_weights:
+            from .prioritized import PrioritizedPopulationReplay as _Prio
+            if not isinstance(replay, _Prio):
+                raise ValueError("importance_weights=True needs replay=PrioritizedPopulationReplay(...): "
+                                 "no other replay computes them")
         cfgs = self.configs = _common_configs(configs)
         P = self.P = len(cfgs)
         cfg = cfgs[0]
@@ -203,8 +215,15 @@ class NativeSACPopulation(_SacCore):
             return None
         return self.sample()
 
-    def learn(self, batch=None, noise=None, *, losses: bool = True):
-        out = super().learn(batch, noise, losses=losses)
+    def learn(self, batch=None, noise=None, *, weights=None, losses: bool = True):
+        if self.importance_weights and batch is None and weights is None:
+            batch = self._sample()                # the replay's own sample, with its weights
+            if batch is None:
+                return None
+            out = super().learn(batch, noise, weights=self.memory.last_weights, losses=losses)
+            self.memory.update_from_learn(self)
+            return out
+        out = super().learn(batch, noise, weights=weights, losses=losses)
         if self._prioritized and batch is None and out is not None:
             self.memory.update_from_learn(self)   # the batch was the replay's last sample
         return out

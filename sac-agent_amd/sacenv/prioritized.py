@@ -7,8 +7,11 @@ The priorities live in a buffer of their own (``prio``, ``[P, member_bytes]``); 
 byte for byte a plain ``PopulationReplay``'s. A store marks the rows it writes with the largest
 priority seen so far, a sample is a draw on the trees and the population gather, and after a learn
 ``update_from_learn`` turns the per-row squared TD errors the learn kernels leave in their scratch
-into new priorities -- the learn kernels themselves are not touched, and the importance weights a
-sample computes (``last_weights``) are NOT applied inside them. Priorities are u32 fixed point
+into new priorities. The importance weights a sample computes (``last_weights``) are applied in
+the critic loss with ``importance_weights=True`` (``NativeSACPopulation``; ``--importance-weights``
+in examples/train_population.py; include/sacenv_weighted_learn.h), and not without it; their
+exponent is ``beta``, or with ``beta_final`` / ``beta_anneal`` runs from ``beta`` to ``beta_final``
+over ``beta_anneal`` samples, derived on the device from the sample's number. Priorities are u32 fixed point
 (65 536 = 1.0) and node sums u64, so the tree and every drawn index are reproducible bit for bit
 (tests/prio_oracle.py). Whether prioritizing speeds learning up has not been measured.
 
@@ -35,13 +38,27 @@ class PrioritizedPopulationReplay(PopulationReplay):
     ``prio_seeds``: one Philox seed per member for the draws (default: the members' ``seeds``)."""
 
     def __init__(self, members: int, max_size: int, input_shape, n_actions: int, *, alpha: float = 0.6,
-                 beta: float = 0.4, eps: float = 1e-3, prio_seeds=None, **kw):
+                 beta: float = 0.4, eps: float = 1e-3, prio_seeds=None, beta_final: float | None = None,
+                 beta_anneal: int = 0, **kw):
         fns = _lib.require(_lib.REPLAY_PRIO_EXPORTS, _HEADER)
         (_, self._init, self._mark, self._set, self._update_td, self._learn_rows, self._sample) = fns
         for name, v in (("alpha", alpha), ("beta", beta), ("eps", eps)):
             if not (math.isfinite(v) and v >= 0):
                 raise ValueError(f"{name} must be finite and >= 0, got {v}")
         self.alpha, self.beta, self.eps = float(alpha), float(beta), float(eps)
+        # the weights' exponent annealed from beta to beta_final over beta_anneal samples, on the
+        # device (include/sacenv_weighted_learn.h); without beta_final nothing changes
+        self.beta_final, self.beta_anneal, self._sample_annealed = None, 0, None
+        if beta_final is not None:
+            if not (math.isfinite(beta_final) and beta_final >= 0):
+                raise ValueError(f"beta_final must be finite and >= 0, got {beta_final}")
+            if int(beta_anneal) < 1:
+                raise ValueError(f"beta_final needs beta_anneal >= 1 (the samples the exponent takes to reach "
+                                 f"it), got {beta_anneal}")
+            self.beta_final, self.beta_anneal = float(beta_final), int(beta_anneal)
+            self._sample_annealed = _lib.weighted_learn_fn("sacenv_replay_prio_sample_annealed")
+        elif beta_anneal:
+            raise ValueError("beta_anneal needs beta_final")
         super().__init__(members, max_size, input_shape, n_actions, **kw)
         P = self.P
         self.prio_seeds = list(self.seeds) if prio_seeds is None else [int(s) for s in prio_seeds]
@@ -86,14 +103,30 @@ class PrioritizedPopulationReplay(PopulationReplay):
         st, ac, rw, ns, tm, idx = self._outputs(B, idx=True)
         leaf = torch.empty(self.P, B, dtype=torch.int32, device=self.device)
         w = torch.empty(self.P, B, dtype=torch.float32, device=self.device)
-        _lib.check(self._sample(self._pp, self.P, self.arena.data_ptr(), self.prio.data_ptr(), B,
-                                -1 if graph_safe else self.sample_calls, self._prio_seeds, idx.data_ptr(),
-                                leaf.data_ptr(), w.data_ptr(), self.beta, st.data_ptr(), ac.data_ptr(), rw.data_ptr(),
-                                ns.data_ptr(), tm.data_ptr(), self.stream))
+        if self._sample_annealed is None:
+            _lib.check(self._sample(self._pp, self.P, self.arena.data_ptr(), self.prio.data_ptr(), B,
+                                    -1 if graph_safe else self.sample_calls, self._prio_seeds, idx.data_ptr(),
+                                    leaf.data_ptr(), w.data_ptr(), self.beta, st.data_ptr(), ac.data_ptr(),
+                                    rw.data_ptr(), ns.data_ptr(), tm.data_ptr(), self.stream))
+        else:   # beta_at(the sample's number), computed on the device
+            _lib.check(self._sample_annealed(
+                self._pp, self.P, self.arena.data_ptr(), self.prio.data_ptr(), B,
+                -1 if graph_safe else self.sample_calls, self._prio_seeds, idx.data_ptr(), leaf.data_ptr(),
+                w.data_ptr(), self.beta, self.beta_final, self.beta_anneal, st.data_ptr(), ac.data_ptr(),
+                rw.data_ptr(), ns.data_ptr(), tm.data_ptr(), self.stream))
         if B > 0 and not graph_safe:
             self.sample_calls += 1
         self.last_idx, self.last_leaf, self.last_weights = idx, leaf, w
         return st, ac, rw, ns, (tm.bool() if as_bool else tm), idx
+
+    def beta_at(self, k: int) -> float:
+        """The weights' exponent of sample number ``k`` (``sample_calls``, or with ``graph_safe``
+        ``header(m)["calls"]``, before the sample): ``beta`` without ``beta_final``, else in f64
+        ``beta + (beta_final - beta) * (min(k, beta_anneal) / beta_anneal)``, as the device forms it."""
+        if self.beta_final is None:
+            return self.beta
+        n = self.beta_anneal
+        return self.beta + (self.beta_final - self.beta) * (min(int(k), n) / n)
 
     def sample_pool(self, batch_size: int, pool_rows: int, as_bool: bool = True):
         raise ValueError("a prioritized replay does not pool: pool_rows must be 0")

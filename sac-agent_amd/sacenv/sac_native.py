@@ -210,15 +210,32 @@ class _SacCore:
             raise RuntimeError("act_noise needs noise seeds (noise_seed= / noise_seeds=)")
         return self.noise.normal(ACT, self.act_calls, n, calls=K).view(K, *self.lead, n)
 
+    _learn_weighted = None   # the entry point of sacenv_weighted_learn.h, bound at the first weighted learn
+
+    def _row_weights(self, weights):
+        """``weights`` as the kernels read them; the shape is checked before a device is touched."""
+        want = (*self.lead, self._B)
+        shape = tuple(getattr(weights, "shape", None) or torch.as_tensor(weights).shape)
+        if shape != want:
+            raise ValueError(f"weights must be {_shape(*want)}, got {list(shape)}")
+        if self._learn_weighted is None:
+            self._learn_weighted = _lib.weighted_learn_fn(self._learn_weighted_name)
+        return self._f32(weights, self._agents * self._B, "weights")
+
     @torch.no_grad()
-    def learn(self, batch=None, noise=None, *, losses: bool = True):
+    def learn(self, batch=None, noise=None, *, weights=None, losses: bool = True):
         """continuous_agent.py:96-154 as VecSAC.learn, for every agent. ``batch`` = (state
         ``[*lead, B, D]``, action ``[*lead, B(, 1)]``, reward ``[*lead, B]``, new_state, done);
         else the agents' own replay memory is sampled (None while it holds < B rows). ``noise``
-        = (eps1, eps2), each ``[*lead, B(, 1)]``. Returns the (value, actor, critic 1, critic 2)
+        = (eps1, eps2), each ``[*lead, B(, 1)]``. ``weights``: f32 ``[*lead, B]``, a weight per
+        batch row on the critics' TD loss (include/sacenv_weighted_learn.h: the importance weights
+        of a prioritized sample; the per-row squared TD errors in the scratch stay raw); ``None``
+        is the unweighted call. Returns the (value, actor, critic 1, critic 2)
         losses as independent tensors -- the one agent's as four device scalars, a population's
         as ``[P, 4]`` -- or with ``losses=False`` the f32 ``[*lead, 4]`` loss buffer itself (no
         copy launch: the next learn() rewrites it)."""
+        if weights is not None:
+            weights = self._row_weights(weights)
         B, k = self._B, self._k
         if batch is None:
             batch = self._sample()
@@ -242,10 +259,16 @@ class _SacCore:
         else:
             e1, e2 = torch.randn((*self.lead, B), device=self.device), torch.randn((*self.lead, B), device=self.device)
         step = self.adam_step + 1  # committed only once the call is accepted
-        _lib.check(self._learn(
-            *self._learn_head, self.weights.data_ptr(), self.scratch.data_ptr(), state.data_ptr(),
-            action.data_ptr(), reward.data_ptr(), state_.data_ptr(), done.data_ptr(), e1.data_ptr(),
-            e2.data_ptr(), step, self.losses.data_ptr(), self._stream()))
+        if weights is None:
+            _lib.check(self._learn(
+                *self._learn_head, self.weights.data_ptr(), self.scratch.data_ptr(), state.data_ptr(),
+                action.data_ptr(), reward.data_ptr(), state_.data_ptr(), done.data_ptr(), e1.data_ptr(),
+                e2.data_ptr(), step, self.losses.data_ptr(), self._stream()))
+        else:
+            _lib.check(self._learn_weighted(
+                *self._learn_head, self.weights.data_ptr(), self.scratch.data_ptr(), state.data_ptr(),
+                action.data_ptr(), reward.data_ptr(), state_.data_ptr(), done.data_ptr(), e1.data_ptr(),
+                e2.data_ptr(), step, self.losses.data_ptr(), weights.data_ptr(), self._stream()))
         self.adam_step = step
         if not losses:
             return self.losses
@@ -255,6 +278,8 @@ class _SacCore:
 
 class NativeSAC(_SacCore, SlabNets):
     """ContinuousAgent (continuous_agent.py:9-154) on libsacenv's SAC kernels."""
+
+    _learn_weighted_name = "sacenv_sac_learn_weighted"
 
     def __init__(self, device, config=None, *, obs_dim: int = 11, n_actions: int = 1,
                  max_action: float = 1.0, init_seed: int | None = None, buffer_seed: int = 0,
