@@ -92,12 +92,15 @@ class Tree:
         self.set(idx, td_leaves(sq1, sq2, alpha, eps))
 
     # ---- the draw
-    def draw(self, B: int, call: int, m: int, seed: int, descend: bool = True):
+    def draw(self, B: int, call: int, m: int, seed: int, descend: bool = True, total: int | None = None):
         """(idx [B] i64, leaf [B] u32, t [B] python ints) of one sample. ``descend=False`` finds
         each row in the running sum of the leaves instead of walking the levels: the same rows,
         since every node is the exact sum of its children (tests/test_prioritized_replay_cpu.py
-        holds the two against each other), and much faster for a population's worth of draws."""
-        levels, T = self.levels(), self.total()
+        holds the two against each other), and much faster for a population's worth of draws.
+        ``total``: the header's total where it is not the leaves' sum (a tree that does not add up);
+        a slot whose t reaches past the leaves' sum finds no child at the top level: idx -1, leaf 0."""
+        levels, real = self.levels(), self.total()
+        T = real if total is None else int(total)
         idx, leaf, ts = np.full(B, -1, np.int64), np.zeros(B, np.uint32), []
         if T == 0 or B == 0:
             return idx, leaf, ts
@@ -110,7 +113,7 @@ class Tree:
             lo, hi = stratum(T, B, j)
             t = lo + ((int(words[j]) * (hi - lo)) >> 64)
             ts.append(t)
-            if not descend:
+            if not descend or t >= real:
                 continue
             node = 0
             for lv in reversed(levels):
@@ -126,8 +129,9 @@ class Tree:
             idx[j], leaf[j] = node, self.leaf[node]
         if not descend:
             run = np.cumsum(np.array(self.leaf, np.uint64))          # (exact: T < 2^62)
-            idx = np.searchsorted(run, np.array(ts, np.uint64), side="right").astype(np.int64)
-            leaf = np.array(self.leaf, np.uint32)[idx]
+            at = np.searchsorted(run, np.array(ts, np.uint64), side="right").astype(np.int64)
+            hit = at < self.M                                         # (t < the leaves' sum)
+            idx[hit], leaf[hit] = at[hit], np.array(self.leaf, np.uint32)[at[hit]]
         return idx, leaf, ts
 
 
@@ -157,6 +161,47 @@ def td_leaves(sq1, sq2, alpha: float, eps: float) -> np.ndarray:
     return out
 
 
+def td_leaves_mp(sq1, sq2, alpha: float, eps: float, prec: int = 160):
+    """(leaf u32 [n], decided bool [n]): ``td_leaves``' rule on the exact real numbers, in mpmath at
+    ``prec`` >= 160 bits. The f32 inputs are taken exactly, ``alpha`` and ``eps`` as the f64 values
+    passed; a = 0.5 (sqrt(sq1) + sqrt(sq2)) + eps (``sq2`` None: sqrt(sq1) + eps), s = a^alpha 65536,
+    leaf = clamp(floor(s), 1, 2^31 - 1). A NaN or negative input (-0.0 is not negative) gives 1;
+    alpha == 0 gives 65 536 for every other a, 0 and +inf included; a +inf input the cap; a == 0 gives 1.
+
+    A row is undecided where s lies within s 2^-44 of an integer of [1, 2^31] (the thresholds 1 and
+    2^31 - 1 among them): a chain of two square roots, two adds and a pow in f64, each within about
+    an ulp and amplified by alpha <= 2, stays within a few 2^-52 s of s, and 2^-44 is more than 100
+    times that. On a decided row every such chain gives this leaf; on the others it may give the
+    next integer. alpha == 0 rows are decided: pow(x, 0) is exactly 1."""
+    import mpmath
+    assert prec >= 160
+    x1 = np.asarray(sq1, np.float32).astype(np.float64).ravel()
+    x2 = None if sq2 is None else np.asarray(sq2, np.float32).astype(np.float64).ravel()
+    alpha, eps = float(alpha), float(eps)
+    assert alpha >= 0 and eps >= 0 and (x2 is None or x2.shape == x1.shape)
+    leaf, decided = np.ones(x1.size, np.uint32), np.ones(x1.size, bool)
+    with mpmath.workprec(prec):
+        al, ep, margin = mpmath.mpf(alpha), mpmath.mpf(eps), mpmath.ldexp(1, -44)
+        for i in range(x1.size):
+            xs = [float(x1[i])] + ([] if x2 is None else [float(x2[i])])
+            if any(np.isnan(x) or x < 0 for x in xs):
+                continue                                             # 1
+            if alpha == 0:
+                leaf[i] = ONE
+                continue
+            if any(np.isinf(x) for x in xs):
+                leaf[i] = CAP
+                continue
+            a = sum(mpmath.sqrt(mpmath.mpf(x)) for x in xs) / len(xs) + ep
+            if a == 0:
+                continue                                             # 1
+            s = mpmath.power(a, al) * ONE
+            n = int(mpmath.nint(s))
+            decided[i] = not (1 <= n <= 1 << 31 and abs(s - n) <= s * margin)
+            leaf[i] = min(max(int(mpmath.floor(s)), 1), CAP)
+    return leaf.reshape(np.shape(sq1)), decided.reshape(np.shape(sq1))
+
+
 def weights(leaf, beta: float) -> np.ndarray:
     """(min leaf / leaf)^beta in f64, rounded once to f32; 0 where the leaf is 0."""
     leaf = np.asarray(leaf, np.uint32)
@@ -176,5 +221,5 @@ def ulp_distance_f32(a, b) -> np.ndarray:
     return np.abs(ia - ib)
 
 
-__all__ = ["Tree", "layout", "level_counts", "stratum", "td_leaves", "weights", "ulp_distance_f32", "FAN", "ONE",
+__all__ = ["Tree", "layout", "level_counts", "stratum", "td_leaves", "td_leaves_mp", "weights", "ulp_distance_f32", "FAN", "ONE",
            "CAP", "KEY1"]
